@@ -2,6 +2,8 @@
 (BASELINE.json metric, configs[1]), 50% keep-set, on 1..8 MI355X (one process per GPU).
 
     python bench.py [--gpus N] [--steps K] [--warmup W]        (starts N ranks itself)
+    python bench.py ... --full                 (adds the rooflines and the CPU baseline)
+    python bench.py ... --dump-outputs DIR     (writes the last timed step's results)
     torchrun --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N ...
 
 With --gpus N > 1 and no torchrun environment, this process is only a launcher: it starts N
@@ -16,9 +18,14 @@ selects the global keep-set (dd_select_topk).  Each rank holds ONLY its shard in
 from the same synthetic set, byte-identical to a slice of it), plus the K models.  Inputs
 are resident in HBM before timing.  Total work is fixed as N grows -> "scaling": "strong".
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with HIP events around the
-dominant hand-written kernel over the timed steps; `cpu_baseline` times the oracle's CPU
-restatement of the reference path (config 1: EL2N, one checkpoint) on a bounded sample.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints the
+headline fields (metric, value, ms_per_step, dtype, config, ...).  `--full` adds the rest:
+`roofline` is measured live with HIP events around the dominant hand-written kernel over the
+timed steps (plus one extra single-lane step when the lanes overlap); `cpu_baseline` times the
+oracle's CPU restatement of the reference path (config 1: EL2N, one checkpoint) on a bounded
+sample.  `--dump-outputs DIR` writes what the last timed step returned (the score vectors, the
+keep-set, k) as DIR/<name>.npy; the inputs are seeded, so two builds given the same arguments
+can be compared output for output.
 """
 from __future__ import annotations
 
@@ -105,13 +112,20 @@ def parse():
     ap.add_argument("--pegrad", default="auto")
     ap.add_argument("--grand-params", default="conv_linear", help="conv_linear | all")
     ap.add_argument("--select-by", default="el2n")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the per-kernel rooflines (HIP events around the timed "
+                         "steps' launches, one extra single-lane step) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's results (scores_<method>, kept, k) as "
+                         "DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip it")
     ap.add_argument("--cpu-el2n-sample", type=int, default=5120)
     ap.add_argument("--cpu-1t-sample", type=int, default=384)
     ap.add_argument("--cpu-grand-sample", type=int, default=256)
     ap.add_argument("--json-out", default=None)
     ap.add_argument("--no-kernel-log", action="store_true",
-                    help="diagnostic: time the steps without per-launch events (no roofline)")
+                    help="diagnostic, with --full: time the steps without per-launch events "
+                         "(no roofline)")
     ap.add_argument("--arch", default="resnet18", help="resnet18 (configs 1-3) | resnet50")
     ap.add_argument("--classes", type=int, default=10, help="10 | 100 (config 4) | 1000")
     ap.add_argument("--imagenet", action="store_true",
@@ -425,6 +439,28 @@ def full_record(args, methods, *, world, rank, elapsed, kept, shard, launcher, r
     }
 
 
+DUMP_MAX_BYTES = 60 * 10**6  # --dump-outputs: every file together stays under 64 MB
+
+
+def dump_outputs(out_dir, full, kept, k):
+    """--dump-outputs: what eng.run returned in the last timed step, as <out_dir>/<name>.npy:
+    scores_<method> (float32, one per example), kept (the keep-set's indices, float64) and k.
+    An array over its share of DUMP_MAX_BYTES is cut to a fixed seeded sample of its elements
+    (in index order), the same sample on every run."""
+    arrays = {f"scores_{m}": v.detach().cpu().numpy().astype(np.float32, copy=False)
+              for m, v in full.items()}
+    arrays["kept"] = kept.cpu().numpy().astype(np.float64)
+    arrays["k"] = np.array([k], dtype=np.float64)
+    share = DUMP_MAX_BYTES // len(arrays)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        cap = share // a.itemsize
+        if a.size > cap:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, cap,
+                                                                      replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 LINE_MAX_BYTES = 8000  # the driver parses the printed line; round 4's 22.6 KB line did not
 
 
@@ -439,14 +475,30 @@ def _sig(x, n=4):
     return x
 
 
+LINE_KEYS = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
+             "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "ranks")
+
+
+def plain_line(full: dict, side_file=None) -> dict:
+    """The printed JSON line of a run without --full: the bench contract's fields, the
+    refinement record and the one-shot wall time (no rooflines, no CPU baseline)."""
+    line = {k: full[k] for k in LINE_KEYS}
+    line["refine"] = full.get("refine")
+    line["one_shot_wall_s"] = (full.get("one_shot") or {}).get("wall_s")
+    if side_file:
+        line["side_file"] = side_file
+    line = _sig(line)
+    line["value"] = full["value"]
+    line["ms_per_step"] = full["ms_per_step"]
+    return line
+
+
 def compact_line(full: dict, side_file=None) -> dict:
-    """The ONE printed JSON line: the bench contract's fields, the dominant kernel's roofline,
-    one short entry per other kernel kind, the CPU baseline and the refinement record.  The
+    """The ONE printed JSON line of a --full run: the bench contract's fields, the dominant
+    kernel's roofline, one short entry per other kernel kind, the CPU baseline and the refinement record.  The
     overlapped timed-region rooflines, the per-shape split and the setup breakdown stay in the
     --json-out side file (`side_file`)."""
-    keep = ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step",
-            "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config", "ranks")
-    line = {k: full[k] for k in keep}
+    line = {k: full[k] for k in LINE_KEYS}
     r = full.get("roofline") or {}
     rl = {k: r[k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic",
                             "avg_launch_us", "launches", "timed_launches",
@@ -559,8 +611,8 @@ def main():
             first_step_s = time.perf_counter() - t
         progress(f"warmup step {i + 1}/{args.warmup}")
     barrier(world)
-    # live per-launch HIP events on the launch stream (timed steps only)
-    _capi.kernel_log = None if args.no_kernel_log else []
+    # --full: live per-launch HIP events on the launch stream (timed steps only)
+    _capi.kernel_log = [] if args.full and not args.no_kernel_log else None
     t0 = time.perf_counter()
     for i in range(args.steps):
         full, kept, k = step()
@@ -573,14 +625,18 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     log, _capi.kernel_log = _capi.kernel_log, None
-    if log is None:
+    if args.dump_outputs and rank == 0:  # every rank holds the gathered scores and keep-set
+        dump_outputs(args.dump_outputs, full, kept, k)
+    if log is None and args.full:
         print(json.dumps({"value": args.n * args.steps / elapsed,
                           "ms_per_step": elapsed / args.steps * 1e3, "kernel_log": False}))
         return
 
-    roofline, extra, kernel_step_s, top_shapes = kernel_report(log, args.steps)
+    roofline = extra = kernel_step_s = top_shapes = None
     roofline_timed, extra_timed, kernel_step_overlapped = None, None, None
-    if args.lanes > 1:
+    if args.full:
+        roofline, extra, kernel_step_s, top_shapes = kernel_report(log, args.steps)
+    if args.full and args.lanes > 1:
         # With lanes > 1 the timed steps' launches overlap, so a launch's duration includes
         # the co-scheduled kernels: the per-kernel rooflines come from one more step on a
         # single lane (same kernels, same shapes, timed alone), the overlapped figures are
@@ -597,7 +653,7 @@ def main():
         roofline, extra, kernel_step_s, top_shapes = kernel_report(log1, 1)
         roofline["measured_on"] = ("one extra single-lane step after the timed region (the "
                                    f"timed steps run {args.lanes} lanes whose launches overlap)")
-    else:
+    elif args.full:
         roofline["measured_on"] = "the timed steps (HIP events around sampled launches)"
 
     value = args.n * args.steps / elapsed
@@ -611,7 +667,7 @@ def main():
                           "why": "selecting pass fp32-grade (f16x3 halves)"
                           if cfg.refine == "auto" else "off"},
                       setup_s=setup_s, phases=phases, first_step_s=first_step_s)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         if images is None:  # config 5: the sample comes back from the device-generated shard
             ns = min(args.cpu_el2n_sample, 128, hi - lo)
             images, labels = img_d[:ns].cpu().numpy(), lab_d[:ns].cpu().numpy()
@@ -624,7 +680,7 @@ def main():
         # ranks the host cores are shared by N GPU processes
         out["cpu_baseline"] = None
     if rank == 0:
-        line = compact_line(out, side_file=args.json_out)
+        line = (compact_line if args.full else plain_line)(out, side_file=args.json_out)
         print(json.dumps(line), flush=True)
         if args.json_out:  # the full record (every kernel kind, timed-region lanes, shapes)
             with open(args.json_out, "w") as f:

@@ -97,3 +97,39 @@ def test_line_drops_small_kinds_before_exceeding_cap(monkeypatch):
     line = bench.compact_line(full)
     assert len(json.dumps(line)) <= 3500
     assert 0 < len(line["rooflines_other"]) < len(bench.KINDS) - 1
+
+
+def test_plain_line_has_the_headline_fields_only():
+    args = _args()
+    full = _full(args)
+    back = json.loads(json.dumps(bench.plain_line(full)))
+    for key in ("metric", "value", "unit", "ms_per_step", "steps", "warmup", "n_gpus", "config",
+                "dtype", "ranks", "refine", "higher_is_better", "scaling", "vs_baseline"):
+        assert key in back, key
+    for key in ("roofline", "rooflines_other", "cpu_baseline", "kernel_time_per_step_s"):
+        assert key not in back, key
+    assert back["value"] == full["value"] and back["ms_per_step"] == full["ms_per_step"]
+    assert back["ms_per_step"] == 119.0 / 20 * 1e3
+
+
+def test_dump_outputs_writes_float_arrays_and_samples_large_ones(tmp_path, monkeypatch):
+    import numpy as np
+    import torch
+    n, k = 1000, 500
+    full = {"el2n": torch.arange(n, dtype=torch.float32), "grand": torch.ones(n)}
+    kept = torch.arange(k, dtype=torch.int64) * 2
+    bench.dump_outputs(str(tmp_path / "a"), full, kept, k)
+    got = {m: np.load(tmp_path / "a" / f"{m}.npy") for m in ("scores_el2n", "scores_grand",
+                                                             "kept", "k")}
+    assert got["scores_el2n"].dtype == np.float32 and got["kept"].dtype == np.float64
+    assert np.array_equal(got["scores_el2n"], np.arange(n)) and got["k"].tolist() == [k]
+    assert np.array_equal(got["kept"], np.arange(k) * 2)
+    # over its share of the byte budget an array becomes a fixed sample, in index order
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 4 * 100)  # 4 arrays x 100 float32
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), full, kept, k)
+    b, c = (np.load(tmp_path / d / "scores_el2n.npy") for d in ("b", "c"))
+    assert b.size == 100 and np.all(np.diff(b) > 0) and np.array_equal(b, c)
+    assert np.load(tmp_path / "b" / "kept.npy").size == 50
+    total = sum(p.stat().st_size for p in (tmp_path / "b").iterdir())
+    assert total <= 4 * 4 * 100 + 4 * 128

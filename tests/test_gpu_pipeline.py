@@ -682,7 +682,7 @@ def test_bench_two_ranks_share_device_prints_one_line(cuda):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2",
                         "--share-device", "--n", "2472", "--ckpts", "2", "--steps", "1",
                         "--warmup", "1"], env=env, cwd=root, capture_output=True, text=True,
                        timeout=600)
@@ -693,6 +693,45 @@ def test_bench_two_ranks_share_device_prints_one_line(cuda):
     assert d["n_gpus"] == 2 and d["ranks"]["world_size"] == 2 and d["ranks"]["backend"] == "gloo"
     assert d["value"] > 0 and d["config"]["kept"] == 1236 and d["cpu_baseline"] is None
     assert d["config"]["shard_examples_rank0"] == 1280
+
+
+def test_bench_plain_run_dumps_last_step_outputs(cuda, tmp_path):
+    """A plain `bench.py --steps 2 --dump-outputs DIR` prints the headline fields only (no
+    rooflines, no CPU baseline) and writes what its last timed step returned: bit-equal to the
+    engine run in-process on the same seeded inputs (n = 1300: a ragged tail, two launch chunks)."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    n, K = 1300, 2
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--n",
+                        str(n), "--ckpts", str(K), "--steps", "2", "--warmup", "0",
+                        "--dump-outputs", str(tmp_path / "out")], env=env, cwd=root,
+                       capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["steps"] == 2 and d["warmup"] == 0 and d["unit"] == "examples/s"
+    assert d["higher_is_better"] is True and d["dtype"].startswith("fp32")
+    assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / (n * 1e3) - 1) < 1e-9
+    for key in ("roofline", "rooflines_other", "cpu_baseline", "kernel_time_per_step_s"):
+        assert key not in d, key
+    got = {os.path.basename(p)[:-4]: np.load(p) for p in glob.glob(str(tmp_path / "out" / "*.npy"))}
+    assert sorted(got) == ["k", "kept", "scores_el2n", "scores_grand"]
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    images, labels = synthetic.make_images(n, 10, seed=0)
+    sds = [synthetic.make_checkpoint("resnet18", 10, seed=s)["net"] for s in range(K)]
+    eng = ScoringEngine(checkpoints.build_models(sds, device=cuda),
+                        ScoreConfig(methods=("el2n", "grand"), grand_batch=1024, el2n_chunk=1024,
+                                    lanes=3), cuda)
+    full, kept, k = eng.run(torch.from_numpy(images).to(cuda), torch.from_numpy(labels).to(cuda),
+                            0.5)
+    assert got["k"].tolist() == [k] and np.array_equal(got["kept"], kept.cpu().numpy())
+    for m in ("el2n", "grand"):
+        assert np.array_equal(got[f"scores_{m}"], full[m].cpu().numpy()), m
 
 
 def test_lanes_are_bitwise_equal_to_one_stream(cuda):

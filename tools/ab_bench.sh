@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 for r in 1 2; do
   for v in A B; do
     L=$LA; E=${ENV_A:-}; [ $v = B ] && { L=$LB; E=${ENV_B:-}; }
-    env $E DD_LIB=$L timeout -k 10 400 python -u bench.py --no-cpu-baseline --steps 3 --warmup 1 "$@" \
+    env $E DD_LIB=$L timeout -k 10 400 python -u bench.py --full --no-cpu-baseline --steps 3 --warmup 1 "$@" \
         --json-out "$OUT/bench_${v}_$r.json" > "$OUT/bench_${v}_$r.log" 2>&1
     rc=$?
     [ $rc -eq 0 ] || { tail -5 "$OUT/bench_${v}_$r.log"; exit $rc; }

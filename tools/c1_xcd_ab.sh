@@ -15,7 +15,7 @@ done
 for r in 1 2; do
   for x in 0 1; do
     DD_C1_XCD=$x timeout -k 10 400 python -u bench.py --arch resnet50 --classes 100 --n 10240 \
-        --steps 2 --warmup 1 --no-cpu-baseline --json-out "$OUT/c4_x${x}_$r.json" \
+        --steps 2 --warmup 1 --full --no-cpu-baseline --json-out "$OUT/c4_x${x}_$r.json" \
         > "$OUT/c4_x${x}_$r.log" 2>&1 || exit 1
     echo "x=$x r=$r $(grep -o '"value": [0-9.]*' "$OUT/c4_x${x}_$r.log" | head -1)"
   done

@@ -35,9 +35,9 @@ for s in $STEPS; do
     smoke)
       run 300 "$OUT/smoke.log" python -u -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' ;;
     bench)
-      run 900 "$OUT/bench.log" python -u bench.py --json-out "$OUT/bench.json" ;;
+      run 900 "$OUT/bench.log" python -u bench.py --full --json-out "$OUT/bench.json" ;;
     dbench)
-      run 900 "$OUT/bench_driver.log" python -u bench.py --gpus 1 --steps 20 --warmup 5 \
+      run 900 "$OUT/bench_driver.log" python -u bench.py --full --gpus 1 --steps 20 --warmup 5 \
           --json-out "$OUT/bench_driver.json" ;;
     final)  # the round's closing measurement set (tools/gpu_round.sh steps)
       bash tools/gpu_round.sh "$TAG" dbench prof pmc busy || exit 1

@@ -46,7 +46,7 @@ for s in $STEPS; do
           --timeout-method thread ;;
     shards)
       for n in 24960 12416 6144; do
-        run 600 "$OUT/bench_shard_$n.log" python -u bench.py --n $n --no-cpu-baseline \
+        run 600 "$OUT/bench_shard_$n.log" python -u bench.py --n $n --full --no-cpu-baseline \
             --json-out "$OUT/bench_shard_n$n.json"
       done ;;
     shards_ab)
@@ -54,33 +54,33 @@ for s in $STEPS; do
       # alternated twice on the same box
       for r in 1 2; do
         for n in 24960 12416 6144; do
-          run 600 "$OUT/bench_shard_even_${n}_$r.log" python -u bench.py --n $n --no-cpu-baseline \
+          run 600 "$OUT/bench_shard_even_${n}_$r.log" python -u bench.py --n $n --full --no-cpu-baseline \
               --steps 3 --even-chunks --json-out "$OUT/bench_shard_even_n${n}_$r.json"
-          run 600 "$OUT/bench_shard_tail_${n}_$r.log" python -u bench.py --n $n --no-cpu-baseline \
+          run 600 "$OUT/bench_shard_tail_${n}_$r.log" python -u bench.py --n $n --full --no-cpu-baseline \
               --steps 3 --json-out "$OUT/bench_shard_tail_n${n}_$r.json"
         done
       done ;;
     w2share)
-      run 600 "$OUT/bench_w2share.log" python -u bench.py --gpus 2 --share-device \
+      run 600 "$OUT/bench_w2share.log" python -u bench.py --full --gpus 2 --share-device \
           --json-out "$OUT/bench_w2share.json" ;;
     smoke)
       run 300 "$OUT/smoke.log" python -u -c 'import __graft_entry__ as g; g.smoke(); print("smoke ok")' ;;
     bench)
-      run 900 "$OUT/bench.log" python -u bench.py --json-out "$OUT/bench.json" ;;
+      run 900 "$OUT/bench.log" python -u bench.py --full --json-out "$OUT/bench.json" ;;
     dbench)
       # the driver's own command line (BENCH_rNN: --steps 20 --warmup 5)
-      run 900 "$OUT/bench_driver.log" python -u bench.py --gpus 1 --steps 20 --warmup 5 \
+      run 900 "$OUT/bench_driver.log" python -u bench.py --full --gpus 1 --steps 20 --warmup 5 \
           --json-out "$OUT/bench_driver.json" ;;
     pmc)
       run 600 "$OUT/pmc.log" bash tools/pmc_bench.sh "$OUT/pmc" ;;
     busy)
       run 300 "$OUT/busy.log" bash tools/pmc_pegrad_busy.sh "$OUT/busy" ;;
     spawn)
-      run 600 "$OUT/bench_spawn.log" python -u bench.py --gpus 1 --spawn --no-cpu-baseline \
+      run 600 "$OUT/bench_spawn.log" python -u bench.py --gpus 1 --spawn --full --no-cpu-baseline \
           --json-out "$OUT/bench_spawn_n1.json" ;;
     prof)
       run 900 "$OUT/prof.log" rocprofv3 --kernel-trace --stats -T --output-format csv \
-          -d "$OUT/prof" -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline \
+          -d "$OUT/prof" -o run -- python3 bench.py --steps 1 --warmup 1 --full --no-cpu-baseline \
           --lanes 1 --json-out "$OUT/bench_under_rocprof.json"
       TRACE=$(find "$OUT/prof" -name '*kernel_trace.csv' | head -1)
       if [ -n "$TRACE" ]; then
@@ -89,10 +89,10 @@ for s in $STEPS; do
         head -25 "$OUT/trace_summary.txt"
       fi ;;
     c4)
-      run 900 "$OUT/c4.log" python -u bench.py --arch resnet50 --classes 100 --steps 1 \
+      run 900 "$OUT/c4.log" python -u bench.py --full --arch resnet50 --classes 100 --steps 1 \
           --warmup 1 --json-out "$OUT/bench_c4.json" ;;
     c5)
-      run 900 "$OUT/c5.log" python -u bench.py --imagenet --arch resnet50 --classes 1000 \
+      run 900 "$OUT/c5.log" python -u bench.py --full --imagenet --arch resnet50 --classes 1000 \
           --ckpts 1 --n 1281167 --steps 1 --warmup 1 --json-out "$OUT/bench_c5.json" ;;
     dropin)
       run 600 "$OUT/dropin.log" python -u tools/bench_dropin.py --json-out "$OUT/dropin.json" ;;

@@ -5,7 +5,7 @@ set -euo pipefail
 export TMPDIR=/tmp
 OUT=${1:-gpurun_out/pmc}
 mkdir -p "$OUT"
-ARGS="--n 2560 --ckpts 1 --steps 1 --warmup 0 --no-cpu-baseline"
+ARGS="--n 2560 --ckpts 1 --steps 1 --warmup 0 --full --no-cpu-baseline"
 for C in FETCH_SIZE WRITE_SIZE; do
   timeout -s KILL 120 rocprofv3 --pmc $C --kernel-include-regex 'pegrad|el2n_rows' -T \
       --output-format csv -d "$OUT/$C" -o run -- python3 bench.py $ARGS > "$OUT/$C.log" 2>&1

@@ -17,7 +17,7 @@ for x in 0 1; do
 done
 for r in 1 2; do
   for x in 0 1; do
-    DD_CONV_XCD=$x timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --no-cpu-baseline \
+    DD_CONV_XCD=$x timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --full --no-cpu-baseline \
         --json-out "$OUT/bench_x${x}_$r.json" > "$OUT/bench_x${x}_$r.log" 2>&1 || exit 1
   done
 done

@@ -7,7 +7,7 @@ OUT=gpurun_out/${1:-xcdl1}
 mkdir -p "$OUT"
 for r in 1 2 3; do
   for x in 0 1; do
-    DD_CONV_XCD=$x timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --no-cpu-baseline \
+    DD_CONV_XCD=$x timeout -k 10 300 python -u bench.py --steps 2 --warmup 1 --full --no-cpu-baseline \
         --lanes 1 --json-out "$OUT/b_x${x}_$r.json" > "$OUT/b_x${x}_$r.log" 2>&1 || exit 1
     python3 -c "
 import json; d=json.load(open('$OUT/b_x${x}_$r.json')); r=d['roofline']
