@@ -453,8 +453,7 @@ int dd_bn_apply_maxpool(const float* y, int64_t B, int32_t C, int32_t h, int32_t
 // DD_BN_QUAD=0: the scalar kernel at every width that is not a multiple of 4 (A/B, tests; read
 // per call)
 static bool quad_on() {
-  const char* e = getenv("DD_BN_QUAD");
-  return !e || atoi(e) != 0;
+  return env_int("DD_BN_QUAD", 1) != 0;
 }
 
 int dd_bn_apply(const float* y, int64_t B, int32_t C, int64_t hw, int32_t group_size,

@@ -1,7 +1,9 @@
 // Shared helpers for libdd.so (gfx950 only): error reporting, launch checks, wave reductions.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <limits.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <stdio.h>
 #include <stdarg.h>
 
@@ -69,6 +71,20 @@ __device__ __forceinline__ float nmax(float v, float f) {
 __device__ __forceinline__ float wave_sum(float v) { return group_sum<kWave>(v); }
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// The DD_* tuning knobs (INTEGRATION.md §5 lists every one): the only environment reads of the
+// library.  A call reads the variable anew, which is what the knobs a process flips between
+// launches need; every other knob is read once per process by caching the call in a
+// function-local static (thread-safe),
+//   static const int v = env_int("DD_CONV_XCD", 1);
+// `dflt` is returned when the variable is unset (kEnvUnset where the default depends on the
+// launch); a set value parses as atoi does.
+constexpr int kEnvUnset = INT_MIN;
+inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+inline const char* env_str(const char* name) { return getenv(name); }
 
 // the weight scale of a split-MFMA pack and the matching accumulator scale of its forward:
 // powers of two (exact to apply and undo); bf16 packs are unscaled

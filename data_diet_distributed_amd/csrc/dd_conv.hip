@@ -2,9 +2,6 @@
 // weight packing, tile selection, and the narrow 32x32 tile of the scoring passes.
 #include "dd_conv_kern.h"
 
-#include <stdlib.h>
-#include <string.h>
-
 namespace dd {
 
 // identity affine for the staging transform (scale 1 at [0], shift 0 at [1]; index mask 0)
@@ -62,65 +59,27 @@ struct Sel {
   int rb, e, na, wo;
   int r2;  // conv3x3_r2_kernel (two workgroups per CU, whole-row register blocking)
 };
-// tuning knob for A/B runs: DD_CONV_TILE=narrow | wide | r2 forces one family where it applies
-static int tile_family() {
-  static int f = -1;
-  if (f < 0) {
-    const char* e = getenv("DD_CONV_TILE");
-    f = !e ? 0 : !strcmp(e, "narrow") ? 1 : !strcmp(e, "wide") ? 2 : !strcmp(e, "r2") ? 3
-        : !strcmp(e, "r2w32") ? 5 : !strcmp(e, "r2sb") ? 6 : 0;
-  }
-  return f;
-}
-
+// A pure function of the shape; the rejected alternatives and their numbers are under
+// profiles/r02_s2 (ab_conv_r2_w32_rejected.txt, ab_conv_r2sb_rejected.txt).
 static bool select(int h, int w, int cout, int gsize, Sel* s) {
-  // wide: 64 o x 64 t per wave; 2 x 2 waves (128 o x 128 t) when the padded outputs allow,
-  // else 1 x 4 (64 o x 256 t)
-  const int wo = pad_to(cout, 64) % 128 == 0 ? 2 : 1;
-  const int tb = (4 / wo) * 64;
-  // measured (tools/ab_conv.py, B = 512): wide wins at 4x4 (512 channels, +16-21 %), narrow
-  // at 8x8 and above (+6-10 % at 256 down to 128 channels, more at 64)
-  const int fam = tile_family();
-  // r2: 128 o x 128 t workgroups (2 x 2 waves of 64 o x 64 t) with cout a multiple of 128.
-  // Measured against the other families (tools/ab_conv.py, B = 1024, profiles/r02_s2): +3-5 %
-  // at 8x8 (256 channels), 0.98x at 4x4 (vs wide), 0.83-0.92x at 16x16 (vs narrow), so by
-  // default at 8x8 only; DD_CONV_TILE=r2 takes it wherever it applies.  (Not at 32x32: the
-  // stem's layout shares that geometry's masks.)
-  // r2: 128 o x 128 t workgroups of 4 waves along o, each 32 o x 128 t (NA = 1, NT = 4), two
+  const bool c128 = pad_to(cout, 64) % 128 == 0;
+  // r2: 128 o x 128 t workgroups of 4 waves along o, each 32 o x 128 t (NT = 4), two
   // workgroups per CU, at 16x16, 8x8 and 4x4 with cout a multiple of 128.  A weight fragment
   // feeds 4 column tiles (twice the narrow tile's), so the weight stream from L2 per MFMA
   // halves.  Measured (tools/ab_conv.py, B = 1024, profiles/r02_s2/ab_conv_r2t.txt): 1.06-1.09x
-  // the narrow tile at 16x16, 1.06x the NA = 2 r2 form at 8x8 (itself 1.03-1.05x narrow),
+  // the narrow tile at 16x16, 1.06x an earlier r2 form at 8x8 that was itself 1.03-1.05x narrow,
   // 1.01-1.03x the wide tile at 4x4; bit-identical.  (Not at 32x32: the stem's layout shares
   // that geometry's masks, and a 256-position tile there would not fit two per CU.)
-  // DD_CONV_TILE=r2w32: at 32x32 with 64 outputs, 4 waves along t, each 64 o x 32 t (NA = 2,
-  // NT = 1: a B fragment feeds both 32-o blocks, a weight fragment one column tile).  Measured
-  // 0.75-0.91x the narrow tile (profiles/r02_s2/ab_conv_r2_w32_rejected.txt): the weight stream
-  // per MFMA, not the B reads, is what costs there, so it is not the default.
-  if (fam == 5 && wo == 1 && w == 32 && h % 4 == 0 && cout <= 64) {
-    *s = {4, 1, 2, 1, 1};
-    return true;
-  }
-  // DD_CONV_TILE=r2sb: at 32x32 with 64 outputs, 2 x 2 waves of 32 o x 128 t (NA = 1, NT = 4:
-  // a weight fragment feeds 4 column tiles), 8-row tiles (1.25x input rows staged instead of
-  // 1.5x), one staging buffer so that two fit per CU.  Measured 0.98-1.01x the narrow tile on
-  // 64 channels and 0.76-0.87x on the stem (profiles/r02_s2/ab_conv_r2sb_rejected.txt): the
-  // 32x32 layers are bound neither by the weight stream nor by the halo re-reads.
-  if (fam == 6 && wo == 1 && w == 32 && h % 8 == 0 && cout <= 64) {
-    *s = {8, 1, 1, 2, 1};
-    return true;
-  }
-  if (wo == 2 && (fam == 3 || fam == 0) && w <= 16) {
+  if (c128 && w <= 16) {
     if (w == 16 && h % 8 == 0) { *s = {8, 1, 1, 4, 1}; return true; }
     if (w == 8 && h == 8 && gsize % 2 == 0) { *s = {8, 2, 1, 4, 1}; return true; }
     if (w == 4 && h == 4 && gsize % 8 == 0) { *s = {4, 8, 1, 4, 1}; return true; }
   }
-  if (fam == 2 || (fam == 0 && w == 4)) {
-    if ((w == 32 || w == 16) && h % (tb / w) == 0) { *s = {tb / w, 1, 2, wo}; return true; }
-    if (w == 8 && h == 8 && gsize % (tb / 64) == 0) { *s = {8, tb / 64, 2, wo}; return true; }
-    if (w == 4 && h == 4 && gsize % (tb / 16) == 0) { *s = {4, tb / 16, 2, wo}; return true; }
-  }
-  // narrow fallbacks
+  // wide (64 o x 64 t per wave, 1 x 4 waves: 64 o x 256 t) at 4x4 where the padded outputs do
+  // not fill the r2 tile's 128: +16-21 % on the narrow tile there (tools/ab_conv.py, B = 512);
+  // narrow wins at 8x8 and above
+  if (!c128 && w == 4 && h == 4 && gsize % 16 == 0) { *s = {4, 16, 2, 1}; return true; }
+  // narrow: 2 x 2 waves of 32 o x TB/2 t; the 32x32 layers, and the fallbacks below them
   if (w == 32 && h % 4 == 0) { *s = {4, 1, 1, 2}; return true; }
   if (w == 16 && h % 8 == 0) { *s = {8, 1, 1, 2}; return true; }
   if (w == 8 && h == 8 && gsize % 2 == 0) { *s = {8, 2, 1, 2}; return true; }
@@ -134,8 +93,7 @@ static bool select(int h, int w, int cout, int gsize, Sel* s) {
 // workgroups of the EL2N statistics launch (the 64-output narrow one at widths past 32); DD_CONV_PW=0 turns it off (read per call, for A/B
 // runs in one process: the caller then takes the implicit GEMM)
 static int pw_tile(int h, int w, int gsize, int* rb, int* e, int* pw) {
-  const char* env = getenv("DD_CONV_PW");
-  if ((env && atoi(env) == 0) || h <= 0 || gsize <= 0) return 0;
+  if (env_int("DD_CONV_PW", 1) == 0 || h <= 0 || gsize <= 0) return 0;
   if (w > 32 && w <= 64 && w % 4 == 0) { *rb = 2; *e = 1; *pw = 1; return 64; }
   if (w > 16 && w <= 32 && w % 4 == 0) { *rb = 4; *e = 1; *pw = 1; return 32; }
   if (w > 8 && w <= 16) { *rb = 8; *e = 1; *pw = 2; return 16; }
@@ -321,7 +279,6 @@ static int forward_impl(const float* x, int64_t B, int32_t cin, int32_t h, int32
   a.kx1 = cin <= conv::kStemCin;  // dd_conv3x3_pack wrote the stem layout
   a.f16 = operands == DD_OPERANDS_F16X3;
   a.acc_scale = acc_scale;
-  a.stagger = conv::stagger_cycles();
   a.xcd = conv::conv_xcd();
   a.relu = relu;
   // ungrouped: one group spanning the batch, a multiple of every tile height

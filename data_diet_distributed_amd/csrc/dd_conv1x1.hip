@@ -701,17 +701,12 @@ inline int c1_epi_code(const Args& a) {
 // DD_C1_ROWQ=0: MODE 2 for the 3x3 / stride-1 shapes MODE 4 takes (A/B; read per launch, so a
 // test can compare the two modes in one process)
 static bool c1_rowq() {
-  const char* e = getenv("DD_C1_ROWQ");
-  return !e || atoi(e) != 0;
+  return env_int("DD_C1_ROWQ", 1) != 0;
 }
 // DD_C1_EPI=0: the run-time-flag epilogue everywhere (A/B)
 static bool c1_epi_specialised() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DD_C1_EPI");
-    v = e ? atoi(e) : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("DD_C1_EPI", 1) != 0;
+  return v;
 }
 
 template <int NA, int WO>
@@ -973,7 +968,7 @@ int gemm_forward(const char* fn, const float* x, int64_t B, int32_t cin, int32_t
   a.f16 = operands == DD_OPERANDS_F16X3;
   a.acc_scale = acc_scale;
   {
-    // read per launch (A/B in one process).  Off by default on the GraNd launches, the
+    // DD_C1_XCD forces it on or off (read once).  Off by default on the GraNd launches, the
     // unit-input launches into fewer than 256 outputs (1-4 % slower with it) and the kh x kw
     // modes: measured neutral on the ResNet-50 1x1 shapes (0.98-1.02x, alternated twice) and
     // on config 4 at N = 10 240 (1926 / 1928 vs 1939 / 1927 ex/s), profiles/r06_s3/c1_xcd/.  On
@@ -981,13 +976,14 @@ int gemm_forward(const char* fn, const float* x, int64_t B, int32_t cin, int32_t
     // rule in launch_any, 0.89x the summed time of config 5's and 0.91x of config 4's shapes
     // (profiles/r06_c5/c1_knobs/); on the unit-input launches into 256 or more outputs too
     // (profiles/r06_c5/c1_knobs_unit/)
-    const char* e = getenv("DD_C1_XCD");
+    static const int forced = env_int("DD_C1_XCD", kEnvUnset);
     const bool plain = !stats && !bias && !residual && !res_up2 && !mask_src && !relu;
-    a.xcd = e ? atoi(e)
-              : (taps == 1 && ((stats && (!xout || conv::pad_to(cout, 64) % 256 == 0)) ||
-                               (plain && conv::pad_to(cout, 64) % 256 == 0))
-                     ? 1
-                     : 0);
+    a.xcd = forced != kEnvUnset
+                ? forced
+                : (taps == 1 && ((stats && (!xout || conv::pad_to(cout, 64) % 256 == 0)) ||
+                                 (plain && conv::pad_to(cout, 64) % 256 == 0))
+                       ? 1
+                       : 0);
   }
   DD_REQUIRE(!xres || xout, "%s: a unit residual needs the unit output", fn);
   DD_REQUIRE(!xres_scale == !xres_shift && (!xres_scale || xres),
@@ -999,11 +995,7 @@ int gemm_forward(const char* fn, const float* x, int64_t B, int32_t cin, int32_t
   a.xres_shift = xres_shift;
   // tile family: DD_C1_FAMILY=1|2|3 forces one for A/B runs (falls back to a narrower one
   // the padded outputs fit); default: the widest that fits
-  static int force = -1;
-  if (force < 0) {
-    const char* e = getenv("DD_C1_FAMILY");
-    force = e ? atoi(e) : 0;
-  }
+  static const int force = env_int("DD_C1_FAMILY", 0);
   return c1::launch_any(a, force, as_stream(stream));
 }
 

@@ -43,9 +43,6 @@
 #endif
 #include "dd_mfma.h"
 
-#include <stdlib.h>
-#include <string.h>
-
 namespace dd {
 namespace conv {
 
@@ -74,9 +71,6 @@ struct Args {
   float acc_scale;        // fp16 packs hold W * 2^s: accumulators are multiplied by 2^-s (exact)
   int xcd;                // XCD-contiguous persistent tile order (DD_CONV_XCD, see conv_xcd)
   int wg;                 // the image width in memory of a padded-width launch (PW tiles)
-  int stagger;            // shader cycles the upper half of the grid waits before its first
-                          // tile (DD_CONV_STAGGER; 0 = off): desynchronises the two resident
-                          // workgroups of a CU so their epilogues do not coincide
   // the fused residual-unit input (staging modes XF >= 2, see kXfOut): the staged value is
   // max(x * in_scale + in_shift + R, in_floor) with R = xres (XF = 3) or xres * xres_scale +
   // xres_shift (XF = 4), and the output-channel block 0 tiles write it to xout once
@@ -92,14 +86,6 @@ struct Args {
 // relu(out), computed while the next unit's first conv stages it)
 constexpr int kXfNone = 0, kXfAffine = 1, kXfOut = 2, kXfOutRes = 3, kXfOutResAff = 4;
 
-// the upper half of a persistent grid starts `cycles` later (see Args::stagger)
-__device__ __forceinline__ void stagger_start(int cycles) {
-  if (cycles > 0 && blockIdx.x >= (gridDim.x >> 1)) {
-    const uint64_t t0 = __builtin_amdgcn_s_memtime();
-    while (__builtin_amdgcn_s_memtime() - t0 < (uint64_t)cycles) __builtin_amdgcn_s_sleep(8);
-  }
-}
-
 // XCD-contiguous tile order of the persistent grids (default; DD_CONV_XCD=0 turns it off):
 // workgroup p starts at logical tile xcd_order(p, grid) and walks +grid, so at any moment each
 // XCD works on one contiguous run of tiles -- the output-channel blocks of a position block
@@ -110,17 +96,7 @@ __device__ __forceinline__ void stagger_start(int cycles) {
 // 1.04x at 16x16, 1.94 -> 1.34x at 8x8 (4x4 and the stem unchanged); time 0.98-0.99x per shape
 // (alternated twice), whole job within 0.4 %.
 inline int conv_xcd() {
-  const char* e = getenv("DD_CONV_XCD");
-  return e ? atoi(e) : 1;
-}
-
-inline int stagger_cycles() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DD_CONV_STAGGER");
-    v = e ? atoi(e) : 0;
-    if (v < 0) v = 0;
-  }
+  static const int v = env_int("DD_CONV_XCD", 1);
   return v;
 }
 
@@ -233,7 +209,6 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void conv3x3_kernel(const Arg
   const int HW = H * WG;
   const int HWP = PW ? A.n_tb * RB * W : HW;  // the padded plane (BN-partial layout)
   const int ntiles = A.n_tiles;
-  stagger_start(A.stagger);
 
   // wave-uniform indices in SGPRs (weight addresses are then a scalar base + lane offset)
   const int tid = threadIdx.x, lane = tid & 63;
@@ -773,10 +748,10 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void conv3x3_kernel(const Arg
   }
 }
 
-// Tiles at two workgroups per CU with whole-row register blocking ("r2"): a wave owns NA 32-o
-// blocks x NT 32-position tiles (the default form: NA = 1, NT = 4, four waves along o), so each
-// weight fragment loaded from L2 feeds NT column tiles.  What keeps it within the 256-register
-// budget with a long weight prefetch:
+// Tiles at two workgroups per CU with whole-row register blocking ("r2"): a wave owns one 32-o
+// block x NT 32-position tiles (NT = 4, four waves along o), so each weight fragment loaded
+// from L2 feeds NT column tiles.  What keeps it within the 256-register budget with a long
+// weight prefetch:
 //   * weights are held one tap row at a time in two register sets instead of a chunk's 9 taps:
 //     after a tap's MFMAs its slot is refilled with the same kx two tap rows ahead (5 taps of
 //     MFMAs of prefetch distance; row r + 2 of a chunk is row r - 1 of the next);
@@ -787,22 +762,18 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void conv3x3_kernel(const Arg
 // chunk when cin / 16 is odd: its staged rows are zeros, its weight loads clamped).  Staging
 // (the stem layout included: its chunks run the kx = 1 taps only), fragment order, mask and
 // statistics layouts are those of conv3x3_kernel.
-// SB: one LDS staging buffer (for tiles whose double buffer would not fit two per CU): a
-// chunk's prefetched rows are stored between two barriers after its MFMAs, so the staging
-// overlaps the other workgroup's MFMAs instead of its own; the epilogue blocks sit past it.
 // PW (padded width): the EL2N statistics launches at a width that is not a tile width (the
 // ImageNet-stem network's 28 / 14 / 7 maps).  The tile keeps its W-wide LDS image; the image in
 // memory is WG = A.wg <= W wide, and its columns >= WG and rows >= H (the last row block may
 // overhang) are staged as zeros and never stored or counted.  PW = 1: WG % 4 == 0 (float4 loads
 // and stores, as the native tiles); PW = 2: any WG (rows are not 16-byte aligned: dword loads
 // and stores).  BN partials keep the native layout on the padded grid (32 positions each).
-template <int W, int RB, int E, int NA, int WO, int XF, bool KX1, bool SB, int EPI = 0, int PW = 0>
+template <int W, int RB, int E, int WO, int XF, bool KX1, int EPI = 0, int PW = 0>
 __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
-  using C = Cfg<W, RB, E, NA, WO>;
+  using C = Cfg<W, RB, E, 1, WO>;
   constexpr int NT = C::NT;
   constexpr bool F16 = (EPI & kEpiF16) != 0;
-  static_assert(!PW || (XF <= kXfAffine && !KX1 && !SB &&
-                        (EPI & ~kEpiF16) == (kEpiSpec | kEpiStats)),
+  static_assert(!PW || (XF <= kXfAffine && !KX1 && (EPI & ~kEpiF16) == (kEpiSpec | kEpiStats)),
                 "padded-width tiles: the statistics epilogue with an optional BN staging only");
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int H = A.H, cin = A.cin, cout = A.cout;
@@ -812,7 +783,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
   const int HW = H * WG;
   const int HWP = PW ? A.n_tb * RB * W : HW;  // the padded plane (BN-partial layout)
   const int ntiles = A.n_tiles;
-  stagger_start(A.stagger);
 
   // wave-uniform indices in SGPRs (weight addresses are then a scalar base + lane offset)
   const int tid = threadIdx.x, lane = tid & 63;
@@ -834,7 +804,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
     T.y0 = T.tb * RB;
     T.grp = T.b / A.gsize;
     T.xf_base = (int)(T.grp * cin);
-    T.ob32 = (T.o0 >> 5) + wo * NA;
+    T.ob32 = (T.o0 >> 5) + wo;
     return T;
   };
 
@@ -905,7 +875,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
     }
   };
   auto store_chunk = [&](int buf) {
-    char* base0 = smem + (SB ? 0 : buf) * C::BUF;
+    char* base0 = smem + buf * C::BUF;
 #pragma unroll
     for (int k = 0; k < C::NST; ++k) {
       const int q = tid + 256 * k;
@@ -958,23 +928,20 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
     }
   };
 
-  // ---- weights: two sets of one tap row each, [set][a][kx][hi|lo]
+  // ---- weights: two sets of one tap row each, [set][kx][hi|lo]
   const int nkc = (cin + CC - 1) / CC;
   const int nk2 = (nkc + 1) & ~1;
-  bf16x8 ws[2][NA][3][2];
+  bf16x8 ws[2][3][2];
   const int nob32 = A.op >> 5;
   const __bf16* __restrict__ wpack = A.wpack;
   // (the stem layout uses the kx = 1 taps only)
   auto load_tap = [&](int set, int ob32, int kc, int ky, int kx) {
     if (KX1 && kx != 1) return;
     const int k = kc < nkc ? kc : nkc - 1;  // the zero chunk's weights: any finite values
-#pragma unroll
-    for (int a = 0; a < NA; ++a) {
-      const __bf16* base =
-          wpack + ((size_t)(k * nob32 + ob32 + a) * 18 + (ky * 3 + kx) * 2) * 512 + lane * 8;
-      ws[set][a][kx][0] = *reinterpret_cast<const bf16x8*>(base);
-      ws[set][a][kx][1] = *reinterpret_cast<const bf16x8*>(base + 512);
-    }
+    const __bf16* base =
+        wpack + ((size_t)(k * nob32 + ob32) * 18 + (ky * 3 + kx) * 2) * 512 + lane * 8;
+    ws[set][kx][0] = *reinterpret_cast<const bf16x8*>(base);
+    ws[set][kx][1] = *reinterpret_cast<const bf16x8*>(base + 512);
   };
 
   const int q = (lane >> 2) & 3, p = lane & 3, g1 = (lane >> 4) & 1;
@@ -986,35 +953,31 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
     tr_off[n] = e * C::IMGP + ((t / W) % RB) * C::ROWP + (8 * h + q) * C::XS + (t % W) * 2;
   }
 
-  floatx16 acc[NA][NT];
+  floatx16 acc[NT];
   // B fragments [n][hi|lo], one tap at a time: column tile n of the next tap is read as soon as
-  // this tap's MFMAs on column tile n have issued (NA x 3 MFMAs of distance)
+  // this tap's MFMAs on column tile n have issued (3 MFMAs of distance)
   bf16x8 bb[NT][2];
   auto read_b = [&](int buf, int ky, int kx, int n) {
-    const char* a = smem + (SB ? 0 : buf) * C::BUF + ky * C::ROWP + (kx * 2) * C::PLANE + tr_off[n];
+    const char* a = smem + buf * C::BUF + ky * C::ROWP + (kx * 2) * C::PLANE + tr_off[n];
     bb[n][0] = tr_read8(a, a + 4 * C::XS);
     bb[n][1] = tr_read8(a + C::PLANE, a + C::PLANE + 4 * C::XS);
   };
   auto mfma_b = [&](int set, int kx, int n) {
-#pragma unroll
-    for (int a = 0; a < NA; ++a) {
-      floatx16 d = acc[a][n];
-      d = mfma16<F16>(ws[set][a][kx][0], bb[n][0], d);
-      d = mfma16<F16>(ws[set][a][kx][0], bb[n][1], d);
-      d = mfma16<F16>(ws[set][a][kx][1], bb[n][0], d);
-      acc[a][n] = d;
-    }
+    floatx16 d = acc[n];
+    d = mfma16<F16>(ws[set][kx][0], bb[n][0], d);
+    d = mfma16<F16>(ws[set][kx][0], bb[n][1], d);
+    d = mfma16<F16>(ws[set][kx][1], bb[n][0], d);
+    acc[n] = d;
   };
 
-  // ---- epilogue (conv3x3_kernel's, one A block at a time: the operands of one block are
-  // loaded, then combined and stored, so the live registers stay within the budget)
+  // ---- epilogue (conv3x3_kernel's, two fragments at a time)
   auto epilogue = [&](const Tile& T, int tile, int free_buf) {
     const EpiFlags F = epi_flags<EPI>(A);
     const float* __restrict__ bias = A.bias;
     const float* __restrict__ residual = A.residual;
     const float* __restrict__ mask_src = A.mask_src;
     float* __restrict__ y = A.y;
-    float* ep = reinterpret_cast<float*>(smem + (SB ? 1 : free_buf) * C::BUF) + wv * 1024;
+    float* ep = reinterpret_cast<float*>(smem + free_buf * C::BUF) + wv * 1024;
     const int tl = lane & 7, ol = lane >> 3;
     size_t ibase[NT];
     bool vlan[NT];
@@ -1040,14 +1003,13 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
     // fragments in groups of NG along n: one group's operands are loaded, then combined and
     // stored, so the live registers stay within the budget
     constexpr int NG = NT < 2 ? NT : 2;
-    static_for<NA * (NT / NG)>([&](auto Gc) {
-      constexpr int a = decltype(Gc)::value / (NT / NG);
-      constexpr int n0 = (decltype(Gc)::value % (NT / NG)) * NG;
+    static_for<NT / NG>([&](auto Gc) {
+      constexpr int n0 = decltype(Gc)::value * NG;
       int off[4];
       float bia[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const int o = T.o0 + (wo * NA + a) * 32 + ol + 8 * k;
+        const int o = T.o0 + wo * 32 + ol + 8 * k;
         const int oc = o < cout ? o : cout - 1;
         off[k] = oc * HW;
         bia[k] = F.bias ? bias[oc] : 0.f;
@@ -1081,7 +1043,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
       } else {
 #pragma unroll
         for (int m = 0; m < NG; ++m) {
-          const size_t fidx = ((((size_t)tile * 4 + wv) * NA + a) * NT + n0 + m) * 64 + lane;
+          const size_t fidx = (((size_t)tile * 4 + wv) * NT + n0 + m) * 64 + lane;
           mbits[m] = F.min ? A.mask_in[fidx] : 0xffffu;
         }
       }
@@ -1091,7 +1053,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           ep[((r & 3) + 8 * (r >> 2) + 4 * h) * 32 + (lane & 31)] =
-              F16 ? acc[a][n][r] * A.acc_scale : acc[a][n][r];
+              F16 ? acc[n][r] * A.acc_scale : acc[n][r];
         asm volatile("" ::: "memory");
         float4 v[4];
 #pragma unroll
@@ -1099,7 +1061,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
           v[k] = *reinterpret_cast<const float4*>(ep + (8 * k + ol) * 32 + 4 * tl);
         asm volatile("" ::: "memory");
         const int tt0 = wt * C::TW + n * 32;
-        const int ob = T.o0 + (wo * NA + a) * 32 + ol;
+        const int ob = T.o0 + wo * 32 + ol;
         unsigned obits = 0;
         float* sp = nullptr;  // BN partials of channels ob + 8 k: one base, a constant stride
         if (F.stats) {
@@ -1143,7 +1105,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
           }
         }
         if (F.mout) {
-          const size_t fidx = ((((size_t)tile * 4 + wv) * NA + a) * NT + n) * 64 + lane;
+          const size_t fidx = (((size_t)tile * 4 + wv) * NT + n) * 64 + lane;
           A.mask_out[fidx] = (uint16_t)obits;
         }
       }
@@ -1184,15 +1146,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
         else if constexpr (decltype(W2c)::value)
           load_tap(set, Tw.ob32, kw, 1, kx);
       }
-      if constexpr (t == 6 && !SB) store_chunk(P ^ 1);
+      if constexpr (t == 6) store_chunk(P ^ 1);
 #if DD_R2_FENCE >= 2
       __builtin_amdgcn_sched_barrier(0);
 #endif
     });
-    if constexpr (SB) {
-      __syncthreads();  // every wave is done reading the buffer
-      store_chunk(0);
-    }
     __syncthreads();
   };
   const std::integral_constant<int, 0> I0;
@@ -1213,9 +1171,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
     const int tile_n = tile + (int)gridDim.x;
     const bool has_next = tile_n < ntiles;
 #pragma unroll
-    for (int a = 0; a < NA; ++a)
-#pragma unroll
-      for (int n = 0; n < NT; ++n) acc[a][n] = floatx16{0};
+    for (int n = 0; n < NT; ++n) acc[n] = floatx16{0};
     int c = 0;
     for (; c + 2 < nk2; c += 2) {
       chunk(I0, Y, T, c, T, c + 1, T, c + 1);
@@ -1270,12 +1226,8 @@ constexpr int kE_BwdRes = kE_Bwd | kEpiRes;
 constexpr int kE_BwdSrc = kEpiSpec | kEpiMsrc;
 // DD_CONV_EPI=0: every launch on the generic (run-time) epilogue, for A/B runs
 inline bool epi_specialised() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DD_CONV_EPI");
-    v = e ? atoi(e) != 0 : 1;
-  }
-  return v != 0;
+  static const bool v = env_int("DD_CONV_EPI", 1) != 0;
+  return v;
 }
 
 // the staging mode of a launch (kXf*)
@@ -1338,7 +1290,8 @@ static int dispatch_epi(const Args& a, Go& go) {
 }
 
 // epilogue specialisation where the scoring passes run (the 32x32 narrow tile and the r2
-// tiles); other tile configs (A/B families, odd channel counts) use the generic epilogue
+// tiles); the other tile configs (channel counts the r2 tiles do not take) use the generic
+// epilogue
 template <int W, int RB, int E, int NA, int WO>
 constexpr bool kSpecNarrow = W == 32 && RB == 4 && E == 1 && NA == 1 && WO == 2;
 
@@ -1357,15 +1310,15 @@ struct GoNarrow {
     return DD_OK;
   }
 };
-template <int W, int RB, int E, int NA, int WO, bool SB>
+template <int W, int RB, int E, int WO>
 struct GoR2 {
-  static constexpr int LDS = SB ? Cfg<W, RB, E, NA, WO>::BUF + 16384 : Cfg<W, RB, E, NA, WO>::LDS;
+  static constexpr int LDS = Cfg<W, RB, E, 1, WO>::LDS;
   const Args& a;
   dim3 g;
   hipStream_t st;
   template <int XF, bool KX1, int EPI>
   int run() {
-    constexpr auto K = &conv3x3_r2_kernel<W, RB, E, NA, WO, XF, KX1, SB, EPI>;
+    constexpr auto K = &conv3x3_r2_kernel<W, RB, E, WO, XF, KX1, EPI>;
     lds_attr<K>(LDS);
     K<<<g, 256, LDS, st>>>(a);
     DD_CHECK_LAUNCH("dd_conv3x3_forward");
@@ -1395,11 +1348,10 @@ static int launch(Args a, hipStream_t st) {
   return dispatch_epi<kSpecNarrow<W, RB, E, NA, WO>>(a, go);
 }
 
-template <int W, int RB, int E, int NA, int WO, bool SB = false>
+template <int W, int RB, int E, int WO>
 static int launch_r2(Args a, hipStream_t st) {
-  using C = Cfg<W, RB, E, NA, WO>;
-  constexpr int LDS = SB ? C::BUF + 16384 : C::LDS;
-  static_assert(2 * LDS <= 160 * 1024, "r2 tiles run two workgroups per CU");
+  using C = Cfg<W, RB, E, 1, WO>;
+  static_assert(2 * C::LDS <= 160 * 1024, "r2 tiles run two workgroups per CU");
   DD_REQUIRE(a.H % RB == 0, "dd_conv3x3_forward: H must be a multiple of the row block");
   DD_REQUIRE(a.gsize % E == 0, "dd_conv3x3_forward: group_size %d must be a multiple of %d "
              "(images per tile at %dx%d)", a.gsize, E, a.H, W);
@@ -1412,19 +1364,18 @@ static int launch_r2(Args a, hipStream_t st) {
   a.n_tiles = (int)ntiles;
   // persistent, two workgroups per CU
   const int64_t cap = 2ll * device_cus();
-  GoR2<W, RB, E, NA, WO, SB> go{a, dim3((unsigned)(ntiles < cap ? ntiles : cap)), st};
-  // the default r2 tiles (cout a multiple of 128, one image row block per workgroup at 16x16,
-  // 2 images at 8x8, 8 at 4x4) get the specialised epilogues; the A/B-only 32x32 forms do not
-  constexpr bool spec = NA == 1 && WO == 4 && !SB;
-  // the fused unit input at 16x16 and 8x8 (at 4x4 its residual registers spill)
-  return dispatch_epi<spec, decltype(go), spec && W >= 8>(a, go);
+  GoR2<W, RB, E, WO> go{a, dim3((unsigned)(ntiles < cap ? ntiles : cap)), st};
+  // the r2 tiles (cout a multiple of 128, one image row block per workgroup at 16x16, 2 images
+  // at 8x8, 8 at 4x4) get the specialised epilogues, and the fused unit input at 16x16 and 8x8
+  // (at 4x4 its residual registers spill)
+  return dispatch_epi<true, decltype(go), W >= 8>(a, go);
 }
 
 // the padded-width r2 tiles (conv3x3_r2_kernel PW): the EL2N statistics launch, staged with the
 // producer's BN (+ ReLU) or raw, fp16 or bf16 operand halves; 128-output workgroups, two per CU
 template <int W, int RB, int E, int PW, int XF, int EPI>
 static int run_pw(const Args& a, dim3 g, hipStream_t st) {
-  constexpr auto K = &conv3x3_r2_kernel<W, RB, E, 1, 4, XF, false, false, EPI, PW>;
+  constexpr auto K = &conv3x3_r2_kernel<W, RB, E, 4, XF, false, EPI, PW>;
   lds_attr<K>(Cfg<W, RB, E, 1, 4>::LDS);
   K<<<g, 256, Cfg<W, RB, E, 1, 4>::LDS, st>>>(a);
   DD_CHECK_LAUNCH("dd_conv3x3_forward");

@@ -93,18 +93,18 @@ struct FwdArgs {
 // reads it, so it is never written)
 constexpr int kXmNone = 0, kXmAffine = 1, kXmUnit = 3;
 
-// NA = output-channel blocks of 32 per wave: 1 (workgroup 64 o x 64 t, two per CU) or 2
-// (128 o x 64 t, one per CU with the 512-register budget: every staged B fragment feeds
-// twice the MFMAs).
+// A wave owns one block of 32 output channels; two workgroups per CU.  (Two blocks per wave,
+// one workgroup per CU, measured 3-5 % slower on all three ResNet-18 heads:
+// profiles/r01_v18/experiments/down_na2_ab.txt.)
 // Persistent, as dd_conv.hip's conv3x3_kernel: each workgroup walks tiles blockIdx.x,
 // +gridDim.x, ...; a tile's last K chunk stages the next tile's first chunk, whose weights load
 // after the epilogue, so a tile's prologue (a quarter of the layer2 head's 4-chunk K loop)
 // hides under the previous tile's MFMAs.
 // PT = false: one tile per workgroup (the grid covers every tile; has_next folds to false)
-// WA = waves along o: 2 (2 x 2 waves, each 32 NA o x 32 t) or 4 (4 x 1 waves, each 32 o x 64 t,
-// NA = 1: a workgroup covers 128 outputs of the same staged chunk, so the staging and every
-// weight fragment feed twice the MFMAs; B fragments are then read one tap ahead, column tile
-// by column tile, to stay within the two-workgroups-per-CU register budget)
+// WA = waves along o: 2 (2 x 2 waves, each 32 o x 32 t) or 4 (4 x 1 waves, each 32 o x 64 t:
+// a workgroup covers 128 outputs of the same staged chunk, so the staging and every weight
+// fragment feed twice the MFMAs; B fragments are then read one tap ahead, column tile by
+// column tile, to stay within the two-workgroups-per-CU register budget)
 // EPI = the epilogue, fixed at compile time for the two launch shapes of the scoring passes
 // (a runtime test per flag had split the epilogue into ~60 basic blocks): 1 = train-mode BN
 // statistics of both outputs, no bias or ReLU (EL2N); 2 = bias + ReLU on the main output,
@@ -117,12 +117,11 @@ constexpr int kXmNone = 0, kXmAffine = 1, kXmUnit = 3;
 // wide (input 2 WOG), its columns and rows past the map are staged as zeros and never stored or
 // counted.  PW = 1: WOG % 4 == 0 (float4 loads and stores); 2: WOG even (float4 loads, dword
 // stores); 3: any WOG (dword loads and stores).
-template <int WO, int RB, int E, bool SC, int NA, bool PT, int WA, int EPI = 0, int XM = 0,
+template <int WO, int RB, int E, bool SC, bool PT, int WA, int EPI = 0, int XM = 0,
           bool F16 = false, int PW = 0>
-__global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const FwdArgs A) {
+__global__ __launch_bounds__(256, 2) void down_fwd_kernel(const FwdArgs A) {
   using C = DCfg<WO, RB, E>;
   constexpr int NT = WA == 4 ? 2 : 1;  // 32-position column tiles per wave
-  static_assert(WA == 2 || NA == 1, "four waves along o take one 32-o block each");
   constexpr bool S8 = WO >= 8;
   static_assert(!PW || (!SC && S8 && E == 1 && XM != kXmUnit && EPI == 0),
                 "padded-width heads: the plain EL2N statistics launch");
@@ -150,7 +149,7 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const Fw
     T.b = (int64_t)(bid / A.n_tb) * E;
     T.y0 = T.tb * RB;
     T.grp = T.b / A.gsize;
-    T.o_w = ob * 32 * WA * NA + wo * 32 * NA;  // this wave's first of NA x 32 channels
+    T.o_w = ob * 32 * WA + wo * 32;  // this wave's first of 32 channels
     T.ob32 = T.o_w >> 5;
     return T;
   };
@@ -317,32 +316,25 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const Fw
   };
 
   // ---- weights: 9 taps (hi|lo) of the 3x3 pack, 1 tap of the 1x1 pack, 16 B per lane
-  bf16x8 wa[NA][18], wsc[NA][2];
+  bf16x8 wa[18], wsc[2];
   const __bf16* __restrict__ w3 = A.w3;
   const __bf16* __restrict__ wsp = A.ws;
   auto load_w_taps = [&](int ob32, int kc, int tap0, int ntap) {
+    // a block past the padded outputs re-reads the last one; its outputs are never stored
+    const int blk = min(ob32, A.nob32 - 1);
+    const __bf16* base = w3 + ((size_t)(kc * A.nob32 + blk) * 18) * 512 + lane * 8;
+    // constant trip count (the tap range folds at every call site), so wa stays in VGPRs
 #pragma unroll
-    for (int a = 0; a < NA; ++a) {
-      // blocks past the padded outputs (cout % (64 NA) != 0) re-read the last one; their
-      // outputs are never stored
-      const int blk = min(ob32 + a, A.nob32 - 1);
-      const __bf16* base = w3 + ((size_t)(kc * A.nob32 + blk) * 18) * 512 + lane * 8;
-      // constant trip count (the tap range folds at every call site), so wa stays in VGPRs
-#pragma unroll
-      for (int i = 0; i < 18; ++i)
-        if (i >= 2 * tap0 && i < 2 * (tap0 + ntap))
-          wa[a][i] = *reinterpret_cast<const bf16x8*>(base + i * 512);
-    }
+    for (int i = 0; i < 18; ++i)
+      if (i >= 2 * tap0 && i < 2 * (tap0 + ntap))
+        wa[i] = *reinterpret_cast<const bf16x8*>(base + i * 512);
   };
   auto load_w_sc = [&](int ob32, int kc) {
     if constexpr (SC) {
-#pragma unroll
-      for (int a = 0; a < NA; ++a) {
-        const int blk = min(ob32 + a, A.nob32 - 1);
-        const __bf16* base = wsp + ((size_t)(kc * A.nob32 + blk) * 2) * 512 + lane * 8;
-        wsc[a][0] = *reinterpret_cast<const bf16x8*>(base);
-        wsc[a][1] = *reinterpret_cast<const bf16x8*>(base + 512);
-      }
+      const int blk = min(ob32, A.nob32 - 1);
+      const __bf16* base = wsp + ((size_t)(kc * A.nob32 + blk) * 2) * 512 + lane * 8;
+      wsc[0] = *reinterpret_cast<const bf16x8*>(base);
+      wsc[1] = *reinterpret_cast<const bf16x8*>(base + 512);
     }
   };
   // all 9 taps (+ the shortcut) of chunk kc in tap order, each tap fenced: the waitcnt pass
@@ -366,7 +358,7 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const Fw
     tr_off[n] = e * C::IMGP + 2 * ((t / WO) % RB) * C::ROWP + (8 * h + q) * C::XS + (t % WO) * 2;
   }
 
-  floatx16 acc[NA][NT], acc_s[NA][NT];
+  floatx16 acc[NT], acc_s[NT];
   auto read_b = [&](const char* base, int ky, bf16x8 (&bf)[3][2]) {
 #pragma unroll
     for (int kx = 0; kx < 3; ++kx) {
@@ -377,25 +369,23 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const Fw
   };
   auto mfma_row = [&](int ky, const bf16x8 (&bf)[3][2]) {
 #pragma unroll
-    for (int kx = 0; kx < 3; ++kx)
-#pragma unroll
-      for (int a = 0; a < NA; ++a) {
-        const int tap = ky * 3 + kx;
-        floatx16 d = acc[a][0];
-        d = mfma16<F16>(wa[a][tap * 2], bf[kx][0], d);
-        d = mfma16<F16>(wa[a][tap * 2], bf[kx][1], d);
-        d = mfma16<F16>(wa[a][tap * 2 + 1], bf[kx][0], d);
-        acc[a][0] = d;
-        if constexpr (SC) {
-          if (ky == 1 && kx == 1) {
-            floatx16 s = acc_s[a][0];
-            s = mfma16<F16>(wsc[a][0], bf[1][0], s);
-            s = mfma16<F16>(wsc[a][0], bf[1][1], s);
-            s = mfma16<F16>(wsc[a][1], bf[1][0], s);
-            acc_s[a][0] = s;
-          }
+    for (int kx = 0; kx < 3; ++kx) {
+      const int tap = ky * 3 + kx;
+      floatx16 d = acc[0];
+      d = mfma16<F16>(wa[tap * 2], bf[kx][0], d);
+      d = mfma16<F16>(wa[tap * 2], bf[kx][1], d);
+      d = mfma16<F16>(wa[tap * 2 + 1], bf[kx][0], d);
+      acc[0] = d;
+      if constexpr (SC) {
+        if (ky == 1 && kx == 1) {
+          floatx16 s = acc_s[0];
+          s = mfma16<F16>(wsc[0], bf[1][0], s);
+          s = mfma16<F16>(wsc[0], bf[1][1], s);
+          s = mfma16<F16>(wsc[1], bf[1][0], s);
+          acc_s[0] = s;
         }
       }
+    }
   };
 
   // ---- epilogues: each 32 x 32 fragment (column t = lane & 31 of this wave's 32 positions,
@@ -487,9 +477,7 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const Fw
     const int tile_n = tile + (int)gridDim.x;
     const bool has_next = PT && tile_n < ntiles;
 #pragma unroll
-    for (int a = 0; a < NA; ++a)
-#pragma unroll
-      for (int n = 0; n < NT; ++n) acc[a][n] = acc_s[a][n] = floatx16{0};
+    for (int n = 0; n < NT; ++n) acc[n] = acc_s[n] = floatx16{0};
     // one K chunk; wload = false on a tile's last chunk, whose prefetch target is the next
     // tile's first chunk (its weights load after the epilogue)
     // WA = 4: tap by tap; after a tap's MFMAs the next tap's B fragments of that column tile
@@ -514,17 +502,17 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const Fw
         constexpr int t = decltype(Tc)::value;
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
-          floatx16 d = acc[0][n];
-          d = mfma16<F16>(wa[0][t * 2], bb[n][0], d);
-          d = mfma16<F16>(wa[0][t * 2], bb[n][1], d);
-          d = mfma16<F16>(wa[0][t * 2 + 1], bb[n][0], d);
-          acc[0][n] = d;
+          floatx16 d = acc[n];
+          d = mfma16<F16>(wa[t * 2], bb[n][0], d);
+          d = mfma16<F16>(wa[t * 2], bb[n][1], d);
+          d = mfma16<F16>(wa[t * 2 + 1], bb[n][0], d);
+          acc[n] = d;
           if constexpr (SC && t == 4) {
-            floatx16 s_ = acc_s[0][n];
-            s_ = mfma16<F16>(wsc[0][0], bb[n][0], s_);
-            s_ = mfma16<F16>(wsc[0][0], bb[n][1], s_);
-            s_ = mfma16<F16>(wsc[0][1], bb[n][0], s_);
-            acc_s[0][n] = s_;
+            floatx16 s_ = acc_s[n];
+            s_ = mfma16<F16>(wsc[0], bb[n][0], s_);
+            s_ = mfma16<F16>(wsc[0], bb[n][1], s_);
+            s_ = mfma16<F16>(wsc[1], bb[n][0], s_);
+            acc_s[n] = s_;
           }
           if constexpr (t + 1 < 9) rb(t + 1, n);
         }
@@ -560,11 +548,6 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const Fw
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
         __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-        if constexpr (NA == 2) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-          __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-          __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-        }
       }
       __builtin_amdgcn_sched_barrier(0);
       read_b(base, 2, b0);
@@ -581,20 +564,15 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const Fw
         __builtin_amdgcn_sched_group_barrier(0x100, 2, 1);
         __builtin_amdgcn_sched_group_barrier(0x020, 2, 1);
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-        if constexpr (NA == 2) {
-          __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
-          __builtin_amdgcn_sched_group_barrier(0x020, 2, 1);
-          __builtin_amdgcn_sched_group_barrier(0x008, 2, 1);
-        }
       }
       __builtin_amdgcn_sched_barrier(0);
       mfma_row(2, b0);
       store_chunk(cur ^ 1);
       if (wload) load_w_taps(Tp.ob32, kn, 6, 3);
 #pragma unroll
-      for (int i = 0; i < 9 * NA; ++i) {
+      for (int i = 0; i < 9; ++i) {
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 2);
-        __builtin_amdgcn_sched_group_barrier(0x002, NA == 1 ? 5 : 3, 2);
+        __builtin_amdgcn_sched_group_barrier(0x002, 5, 2);
         __builtin_amdgcn_sched_group_barrier(0x080, 1, 2);
       }
       __builtin_amdgcn_sched_barrier(0);
@@ -611,13 +589,10 @@ __global__ __launch_bounds__(256, NA == 1 ? 2 : 1) void down_fwd_kernel(const Fw
     // the last chunk read buffer (g - 1) & 1; the next tile's first chunk sits in g & 1
     char* ep_buf = smem + ((g - 1) & 1) * C::BUF;
 #pragma unroll
-    for (int a = 0; a < NA; ++a)
-#pragma unroll
-      for (int n = 0; n < NT; ++n) {
-        epilogue(T, acc[a][n], A.main, T.o_w + 32 * a, ep_buf, wt + n, std::true_type{});
-        if constexpr (SC)
-          epilogue(T, acc_s[a][n], A.sc, T.o_w + 32 * a, ep_buf, wt + n, std::false_type{});
-      }
+    for (int n = 0; n < NT; ++n) {
+      epilogue(T, acc[n], A.main, T.o_w, ep_buf, wt + n, std::true_type{});
+      if constexpr (SC) epilogue(T, acc_s[n], A.sc, T.o_w, ep_buf, wt + n, std::false_type{});
+    }
     if constexpr (!PT) break;  // one tile per workgroup: nothing follows
     __syncthreads();  // the next tile's first staging store overwrites the transpose blocks
     // the next tile's weights (re-loading this tile's on the last one) BEFORE the exit test: the
@@ -1142,17 +1117,16 @@ __global__ void pack1x1_kernel(const float* __restrict__ w, int cout, int cin, i
   }
 }
 
-template <int WO, int RB, int E, bool SC, int NA, int WA, int EPI = 0, int XM = 0,
-          bool F16 = false>
+template <int WO, int RB, int E, bool SC, int WA, int EPI = 0, int XM = 0, bool F16 = false>
 static int launch_fwd(FwdArgs a, hipStream_t st) {
   using C = DCfg<WO, RB, E>;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&down_fwd_kernel<WO, RB, E, SC, NA, false, WA, EPI, XM, F16>),
+        reinterpret_cast<const void*>(&down_fwd_kernel<WO, RB, E, SC, false, WA, EPI, XM, F16>),
         hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
     (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&down_fwd_kernel<WO, RB, E, SC, NA, true, WA, EPI, XM, F16>),
+        reinterpret_cast<const void*>(&down_fwd_kernel<WO, RB, E, SC, true, WA, EPI, XM, F16>),
         hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
     attr = true;
   }
@@ -1160,7 +1134,7 @@ static int launch_fwd(FwdArgs a, hipStream_t st) {
   DD_REQUIRE(a.gsize % E == 0, "dd_down_forward: group_size %d must be a multiple of %d",
              a.gsize, E);
   a.n_tb = a.HO / RB;
-  a.n_ob = (int)ceil_div(a.cout, 32 * WA * NA);
+  a.n_ob = (int)ceil_div(a.cout, 32 * WA);
   a.tiles_per_group = (a.gsize / E) * a.n_tb * 2;  // two 32-position partials per tile
   const int64_t ntiles = ceil_div(a.B, E) * a.n_tb * a.n_ob;
   DD_REQUIRE(ntiles < (1ll << 31), "dd_down_forward: too many tiles");
@@ -1170,13 +1144,13 @@ static int launch_fwd(FwdArgs a, hipStream_t st) {
   // +5-9 % at cin = 64 (4 K chunks, the layer2 head), -2.5-4 % at cin = 128 / 256 (the
   // persistent loop costs ~30 VGPRs there), which keep one tile per workgroup.
   const bool pt = a.cin <= 64;
-  const int64_t cap = pt ? (NA == 2 ? 1ll : 2ll) * device_cus() : ntiles;
+  const int64_t cap = pt ? 2ll * device_cus() : ntiles;
   const int64_t grid = ntiles < cap ? ntiles : cap;
   if (pt)
-    down_fwd_kernel<WO, RB, E, SC, NA, true, WA, EPI, XM, F16>
+    down_fwd_kernel<WO, RB, E, SC, true, WA, EPI, XM, F16>
         <<<(unsigned)grid, 256, C::LDS, st>>>(a);
   else
-    down_fwd_kernel<WO, RB, E, SC, NA, false, WA, EPI, XM, F16>
+    down_fwd_kernel<WO, RB, E, SC, false, WA, EPI, XM, F16>
         <<<(unsigned)grid, 256, C::LDS, st>>>(a);
   DD_CHECK_LAUNCH("dd_down_forward");
   return DD_OK;
@@ -1187,7 +1161,7 @@ static int launch_fwd(FwdArgs a, hipStream_t st) {
 template <int WO, int RB, int PW, int XM, bool F16>
 static int launch_fwd_pw(FwdArgs a, hipStream_t st) {
   using C = DCfg<WO, RB, 1>;
-  constexpr auto K = &down_fwd_kernel<WO, RB, 1, false, 1, false, 4, 0, XM, F16, PW>;
+  constexpr auto K = &down_fwd_kernel<WO, RB, 1, false, false, 4, 0, XM, F16, PW>;
   static bool attr = false;
   if (!attr) {
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K),
@@ -1205,39 +1179,20 @@ static int launch_fwd_pw(FwdArgs a, hipStream_t st) {
   return DD_OK;
 }
 
-// channel blocks per wave: 1 by default.  NA = 2 (DD_DOWN_NA=2, where the padded outputs fill
-// 128-channel workgroups) needs 336-344 registers, so one workgroup per CU: measured 3-5 %
-// slower on all three ResNet-18 heads (profiles/r01_v18/experiments/down_na2_ab.txt)
-static int fwd_na(int cout) {
-  static int f = -1;
-  if (f < 0) {
-    const char* e = getenv("DD_DOWN_NA");
-    f = e ? atoi(e) : 0;
-  }
-  return f == 2 && conv::pad_to(cout, 64) % 128 == 0 ? 2 : 1;
-}
-// four waves along o (128-output workgroups) where the padded outputs fill them: 1.13-1.26x
-// the 2 x 2 layout on the three ResNet-18 heads, bit-identical (tools/ab_conv.py --kernel down,
-// B = 1024, profiles/r02_s2/ab_down_fwd_wa4.txt); DD_DOWN_WA=2 keeps the 2 x 2 layout
 // the compile-time epilogue of a launch with the shortcut fused (down_fwd_kernel EPI): 1 / 2
 // for the EL2N / GraNd flag sets, 0 otherwise or with DD_DOWN_EPI=0 (the runtime-flag kernel)
 static int fwd_epi(const Out& m, const Out& s) {
-  static int f = -1;
-  if (f < 0) {
-    const char* e = getenv("DD_DOWN_EPI");
-    f = e ? atoi(e) : 1;
-  }
+  static const int f = env_int("DD_DOWN_EPI", 1);
   if (f == 0 || !s.y) return 0;
   if (!m.bias && !m.relu && m.stats && !s.bias && !s.relu && s.stats) return 1;
   if (m.bias && m.relu && !m.stats && s.bias && !s.relu && !s.stats) return 2;
   return 0;
 }
+// four waves along o (128-output workgroups) where the padded outputs fill them: 1.13-1.26x
+// the 2 x 2 layout on the three ResNet-18 heads, bit-identical (tools/ab_conv.py --kernel down,
+// B = 1024, profiles/r02_s2/ab_down_fwd_wa4.txt); DD_DOWN_WA=2 keeps the 2 x 2 layout
 static int fwd_wa(int cout) {
-  static int f = -1;
-  if (f < 0) {
-    const char* e = getenv("DD_DOWN_WA");
-    f = e ? atoi(e) : 4;
-  }
+  static const int f = env_int("DD_DOWN_WA", 4);
   return f == 4 && conv::pad_to(cout, 64) % 128 == 0 ? 4 : 2;
 }
 
@@ -1284,19 +1239,14 @@ static int launch_bwd2(BwdArgs a, hipStream_t st) {
 // 64-position kernel on the three ResNet-18 heads, bit-identical (tools/ab_conv.py --kernel bwd,
 // B = 1024, profiles/r02_s2/ab_down_bwd2.txt)
 static bool bwd2() {
-  static int f = -1;
-  if (f < 0) {
-    const char* e = getenv("DD_DOWN_BWD");
-    f = e ? atoi(e) : 2;
-  }
+  static const int f = env_int("DD_DOWN_BWD", 2);
   return f == 2;
 }
 
 // padded-width geometry (down_fwd_kernel PW): tile width, row block and PW mode of an output
 // width that is not a tile width, or 0 (DD_DOWN_PW=0 turns them off; read per call)
 static int pw_geometry(int ho, int wo, int* rb, int* pw) {
-  const char* env = getenv("DD_DOWN_PW");
-  if ((env && atoi(env) == 0) || ho <= 0) return 0;
+  if (env_int("DD_DOWN_PW", 1) == 0 || ho <= 0) return 0;
   if (wo > 16 && wo <= 32 && wo % 4 == 0) { *rb = 2; *pw = 1; return 32; }
   if (wo > 8 && wo <= 16 && wo % 2 == 0) { *rb = 4; *pw = 2; return 16; }
   if (wo > 4 && wo <= 8) { *rb = 8; *pw = 3; return 8; }
@@ -1415,11 +1365,7 @@ static int down_forward_impl(const float* x, int64_t B, int32_t cin, int32_t ho,
   a.cout = cout;
   a.nob32 = conv::pad_to(cout, 64) / 32;
   a.gsize = grouped ? group_size : (int)(std::min<int64_t>(B + e, 1 << 30) / e * e);
-  static int xcd = -1;
-  if (xcd < 0) {
-    const char* ev = getenv("DD_DOWN_XCD");
-    xcd = ev ? atoi(ev) : 2;
-  }
+  static const int xcd = env_int("DD_DOWN_XCD", 2);  // (the backward's default is 1)
   a.xcd = xcd;
   hipStream_t st = as_stream(stream);
   const bool sc = packed1x1 != nullptr;
@@ -1454,12 +1400,12 @@ static int down_forward_impl(const float* x, int64_t B, int32_t cin, int32_t ho,
     DD_REQUIRE(!in_scale || xres || !sc,
                "dd_down_forward_unit_input: BN + ReLU staging without a shortcut only");
 #define DD_DOWN_F(WO_, RB_, E_, WA_)                                                          \
-    if (xres) return down::launch_fwd<WO_, RB_, E_, true, 1, WA_, 1, down::kXmUnit, true>(a, st); \
-    if (in_scale) return down::launch_fwd<WO_, RB_, E_, false, 1, WA_, 0, down::kXmAffine, true>(a, st); \
-    if (sc && epi == 1) return down::launch_fwd<WO_, RB_, E_, true, 1, WA_, 1, 0, true>(a, st); \
-    if (sc && epi == 2) return down::launch_fwd<WO_, RB_, E_, true, 1, WA_, 2, 0, true>(a, st); \
-    if (sc) return down::launch_fwd<WO_, RB_, E_, true, 1, WA_, 0, 0, true>(a, st);           \
-    return down::launch_fwd<WO_, RB_, E_, false, 1, WA_, 0, 0, true>(a, st);
+    if (xres) return down::launch_fwd<WO_, RB_, E_, true, WA_, 1, down::kXmUnit, true>(a, st); \
+    if (in_scale) return down::launch_fwd<WO_, RB_, E_, false, WA_, 0, down::kXmAffine, true>(a, st); \
+    if (sc && epi == 1) return down::launch_fwd<WO_, RB_, E_, true, WA_, 1, 0, true>(a, st); \
+    if (sc && epi == 2) return down::launch_fwd<WO_, RB_, E_, true, WA_, 2, 0, true>(a, st); \
+    if (sc) return down::launch_fwd<WO_, RB_, E_, true, WA_, 0, 0, true>(a, st);           \
+    return down::launch_fwd<WO_, RB_, E_, false, WA_, 0, 0, true>(a, st);
 #define DD_DOWN_FW(WO_, RB_, E_) \
     if (wa == 4) { DD_DOWN_F(WO_, RB_, E_, 4) } else { DD_DOWN_F(WO_, RB_, E_, 2) }
     if (wo == 32) { DD_DOWN_FW(32, 2, 1) }
@@ -1474,43 +1420,36 @@ static int down_forward_impl(const float* x, int64_t B, int32_t cin, int32_t ho,
     // shapes only (statistics epilogue; 64-output-wave tiles)
     // (the unit form of the persistent cin <= 64 head spills 7 registers at four waves along
     // o, and is still faster there than two along o: EL2N forward 3.625-3.639 vs 3.681-3.682
-    // ms, profiles/r04_fuse/ab_head_wa.txt; DD_DOWN_XWA=2 takes two, for A/B runs)
-    static int xwa = -1;
-    if (xwa < 0) {
-      const char* e = getenv("DD_DOWN_XWA");
-      xwa = e ? atoi(e) : 4;
-    }
-    const int wa = xres && cin <= 64 && xwa == 2 ? 2 : down::fwd_wa(cout);
+    // ms, profiles/r04_fuse/ab_head_wa.txt)
+    const int wa = down::fwd_wa(cout);
 #define DD_DOWN_X(WO_, RB_, E_)                                                          \
     if (xres) {                                                                          \
       DD_REQUIRE(sc && down::fwd_epi(a.main, a.sc) == 1,                                 \
                  "dd_down_forward_unit_input: the unit form needs the fused shortcut and " \
                  "statistics on both outputs");                                          \
-      return wa == 4 ? down::launch_fwd<WO_, RB_, E_, true, 1, 4, 1, down::kXmUnit>(a, st) \
-                     : down::launch_fwd<WO_, RB_, E_, true, 1, 2, 1, down::kXmUnit>(a, st); \
+      return wa == 4 ? down::launch_fwd<WO_, RB_, E_, true, 4, 1, down::kXmUnit>(a, st) \
+                     : down::launch_fwd<WO_, RB_, E_, true, 2, 1, down::kXmUnit>(a, st); \
     }                                                                                    \
     DD_REQUIRE(!sc, "dd_down_forward_unit_input: BN + ReLU staging without a shortcut only"); \
-    return wa == 4 ? down::launch_fwd<WO_, RB_, E_, false, 1, 4, 0, down::kXmAffine>(a, st) \
-                   : down::launch_fwd<WO_, RB_, E_, false, 1, 2, 0, down::kXmAffine>(a, st);
+    return wa == 4 ? down::launch_fwd<WO_, RB_, E_, false, 4, 0, down::kXmAffine>(a, st) \
+                   : down::launch_fwd<WO_, RB_, E_, false, 2, 0, down::kXmAffine>(a, st);
     if (wo == 32) { DD_DOWN_X(32, 2, 1) }
     if (wo == 16) { DD_DOWN_X(16, 4, 1) }
     if (wo == 8) { DD_DOWN_X(8, 8, 1) }
     DD_DOWN_X(4, 4, 4)
 #undef DD_DOWN_X
   }
-  const int na = down::fwd_na(cout), wa = na == 2 ? 2 : down::fwd_wa(cout);
-  const int epi = na == 2 ? 0 : down::fwd_epi(a.main, a.sc);
+  const int wa = down::fwd_wa(cout);
+  const int epi = down::fwd_epi(a.main, a.sc);
 #define DD_DOWN_SC(WO_, RB_, E_, WA_)                                                  \
-  (epi == 1   ? down::launch_fwd<WO_, RB_, E_, true, 1, WA_, 1>(a, st)                \
-   : epi == 2 ? down::launch_fwd<WO_, RB_, E_, true, 1, WA_, 2>(a, st)                \
-              : down::launch_fwd<WO_, RB_, E_, true, 1, WA_, 0>(a, st))
+  (epi == 1   ? down::launch_fwd<WO_, RB_, E_, true, WA_, 1>(a, st)                \
+   : epi == 2 ? down::launch_fwd<WO_, RB_, E_, true, WA_, 2>(a, st)                \
+              : down::launch_fwd<WO_, RB_, E_, true, WA_, 0>(a, st))
 #define DD_DOWN(WO_, RB_, E_)                                                    \
-  return na == 2 ? (sc ? down::launch_fwd<WO_, RB_, E_, true, 2, 2>(a, st)       \
-                       : down::launch_fwd<WO_, RB_, E_, false, 2, 2>(a, st))     \
-         : wa == 4 ? (sc ? DD_DOWN_SC(WO_, RB_, E_, 4)                           \
-                         : down::launch_fwd<WO_, RB_, E_, false, 1, 4>(a, st))   \
+  return wa == 4 ? (sc ? DD_DOWN_SC(WO_, RB_, E_, 4)                             \
+                       : down::launch_fwd<WO_, RB_, E_, false, 4>(a, st))        \
                  : (sc ? DD_DOWN_SC(WO_, RB_, E_, 2)                             \
-                       : down::launch_fwd<WO_, RB_, E_, false, 1, 2>(a, st))
+                       : down::launch_fwd<WO_, RB_, E_, false, 2>(a, st))
   if (wo == 32) DD_DOWN(32, 2, 1);
   if (wo == 16) DD_DOWN(16, 4, 1);
   if (wo == 8) DD_DOWN(8, 8, 1);
@@ -1580,11 +1519,7 @@ int dd_down_backward(const float* dh, const float* dz, int64_t B, int32_t cout, 
   a.cout = cout;
   a.HO = ho;
   a.nob32 = conv::pad_to(cin, 64) / 32;
-  static int xcd = -1;
-  if (xcd < 0) {
-    const char* ev = getenv("DD_DOWN_XCD");
-    xcd = ev ? atoi(ev) : 1;
-  }
+  static const int xcd = env_int("DD_DOWN_XCD", 1);  // (the forward's default is 2)
   a.xcd = xcd;
   hipStream_t st = as_stream(stream);
   const bool sc = dz != nullptr;

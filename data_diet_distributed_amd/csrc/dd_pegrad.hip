@@ -487,12 +487,12 @@ __device__ __forceinline__ void split4(float4 v, bf16x4& hi, bf16x4& lo) {
               (__bf16)(v.w - (float)h3)};
 }
 
-// TG = 2: two tap groups of 4 waves (taps 0-4 and 5-8), 512 threads: each wave holds 5 (4)
-// tap accumulators instead of 9, so two waves fit per SIMD and each hides the other's LDS
-// latency and barrier waits (at TG = 1 the kernel runs one wave per SIMD with 9 accumulators).
-// ||G||^2 is a sum over taps, so the groups' squared sums add with no exchange of G.
-template <int W, int STR, int TG>
-__global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3_kernel(
+// (One wave per SIMD with 9 tap accumulators.  Two tap groups of 4 waves, 5 / 4 accumulators
+// and two waves per SIMD, measured 0.76x at 32x32 and 0.90x on the persistent 16x16 kernel,
+// profiles/r04_conv/ab_pegrad_tg2_rejected.txt: the second wave re-reads the B fragments and
+// the LDS traffic per MFMA rises, which costs more than the hidden latency gains.)
+template <int W, int STR>
+__global__ __launch_bounds__(256, 1) void pegrad_direct3x3_kernel(
     const float* __restrict__ act, const float* __restrict__ gout, int cin, int cout, int H,
     int n_cblk, int n_oblk, const float* __restrict__ col_scale, float* __restrict__ partial) {
   using C = D3Cfg<W, STR>;
@@ -510,17 +510,15 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3_kernel(
   const float* a_b = act + (size_t)b * cin * HWI;
   const float* g_b = gout + (size_t)b * cout * HW;
 
-  constexpr int NTH = 256 * TG;
-  static_assert(C::NA % TG == 0, "whole staging rounds per tap group");
+  constexpr int NTH = 256;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int wq = wv & 3, tg = __builtin_amdgcn_readfirstlane(wv >> 2);
-  const int wc = wq & 1, wo = wq >> 1, r = lane & 31, h = lane >> 5;
+  const int wc = wv & 1, wo = (wv >> 1) & 1, r = lane & 31, h = lane >> 5;  // 2 x 2 waves
 
   // ---- staging: 2 float4 of activations (one input row slice) + 2 float4 of gradients.
   // Loads are unconditional from clamped addresses and out-of-range values are zeroed when
   // they are converted: a predicated `v = cond ? load : 0` makes hipcc branch around the load
   // and wait vmcnt(0) right behind it, which would serialise the prefetch.
-  constexpr int NAT = C::NA / TG, NGT = 2 / TG;  // float4 per thread: activations, gradients
+  constexpr int NAT = C::NA, NGT = 2;  // float4 per thread: activations, gradients
   float4 ra[NAT], rg[NGT];
   bool va[NAT], vg[NGT];
   auto load_rows = [&](int ir0, int nrows, int tstep) {
@@ -608,10 +606,10 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3_kernel(
     }
   };
 
-  constexpr int NACC = TG == 1 ? 9 : 5;  // accumulators per wave: its tap group's taps
-  floatx16 acc[NACC];
+  constexpr int NTAP = 9;  // one accumulator per tap
+  floatx16 acc[NTAP];
 #pragma unroll
-  for (int i = 0; i < NACC; ++i) acc[i] = floatx16{0};
+  for (int i = 0; i < NTAP; ++i) acc[i] = floatx16{0};
 
   const int nsteps = H / C::R;
   // prologue: input rows -1 .. WIN - 2 (the first window) and the gradients of step 0
@@ -635,28 +633,26 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3_kernel(
     const char* ab = act_lds + ((slot * 3 + kx) * 2) * C::PLANE + (wc * 32 + r) * C::CS + x * 2;
     return *reinterpret_cast<const bf16x8*>(ab + lo * C::PLANE);
   };
-  // one step of tap group (T0, NTAP): NTAP taps from T0 (compile-time, so every fragment
-  // address and accumulator index folds)
-  auto group_step = [&](int y0, int gbuf, int inext, auto T0c, auto NTc) {
-    constexpr int T0 = decltype(T0c)::value, NTAP = decltype(NTc)::value;
+  // one step of the 9 taps (every fragment address and accumulator index folds)
+  auto tap_step = [&](int y0, int gbuf, int inext) {
     bf16x8 bh0, bl0, ah0[NTAP], al0[NTAP], bh1, bl1, ah1[NTAP], al1[NTAP];
     // only B and the first tap of sub-step 0 before its first MFMA; its other reads and
     // sub-step 1's B go two per MFMA gap behind the first NTAP MFMAs, then sub-step 1's A
     // reads one per gap, in this fixed order
     bh0 = frag(y0, gbuf, 0, -1, 0);
     bl0 = frag(y0, gbuf, 0, -1, 1);
-    ah0[0] = frag(y0, gbuf, 0, T0, 0);
-    al0[0] = frag(y0, gbuf, 0, T0, 1);
+    ah0[0] = frag(y0, gbuf, 0, 0, 0);
+    al0[0] = frag(y0, gbuf, 0, 0, 1);
     auto rd = [&](int j) {  // the j-th read behind the MFMAs
       constexpr int J0 = 2 * (NTAP - 1), J1 = J0 + 2, J2 = J1 + 2 * NTAP;
       if (j < J0) {
-        if (j & 1) al0[1 + j / 2] = frag(y0, gbuf, 0, T0 + 1 + j / 2, 1);
-        else ah0[1 + j / 2] = frag(y0, gbuf, 0, T0 + 1 + j / 2, 0);
+        if (j & 1) al0[1 + j / 2] = frag(y0, gbuf, 0, 1 + j / 2, 1);
+        else ah0[1 + j / 2] = frag(y0, gbuf, 0, 1 + j / 2, 0);
       } else if (j < J1) {
         (j == J0 ? bh1 : bl1) = frag(y0, gbuf, 1, -1, j - J0);
       } else if (j < J2) {
-        if ((j - J1) & 1) al1[(j - J1) / 2] = frag(y0, gbuf, 1, T0 + (j - J1) / 2, 1);
-        else ah1[(j - J1) / 2] = frag(y0, gbuf, 1, T0 + (j - J1) / 2, 0);
+        if ((j - J1) & 1) al1[(j - J1) / 2] = frag(y0, gbuf, 1, (j - J1) / 2, 1);
+        else ah1[(j - J1) / 2] = frag(y0, gbuf, 1, (j - J1) / 2, 0);
       }
     };
 #pragma unroll
@@ -693,21 +689,13 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3_kernel(
     __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
     __builtin_amdgcn_sched_barrier(0);
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I5 = std::integral_constant<int, 5>;
   for (int st = 0; st < nsteps; ++st) {
     const int y0 = st * C::R;
     // prefetch the next step's rows (on the last step: clamped, harmless, never read)
     const int inext = STR * y0 + C::WIN - 1;  // first input row past this step's window
     load_rows(inext, C::NEW, st + 1);
     const int gbuf = st & 1;
-    if constexpr (TG == 1) {
-      group_step(y0, gbuf, inext, I0{}, std::integral_constant<int, 9>{});
-    } else if (tg == 0) {
-      group_step(y0, gbuf, inext, I0{}, I5{});
-    } else {
-      group_step(y0, gbuf, inext, I5{}, std::integral_constant<int, 4>{});
-    }
+    tap_step(y0, gbuf, inext);
     __syncthreads();
   }
 
@@ -718,59 +706,30 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3_kernel(
     s2 = sc * sc;
   }
   float v = 0.f;
-  const int ntap = TG == 1 ? 9 : (tg == 0 ? 5 : 4);
 #pragma unroll
-  for (int i = 0; i < NACC; ++i)
+  for (int i = 0; i < NTAP; ++i)
 #pragma unroll
-    for (int k = 0; k < 16; ++k) v += i < ntap ? acc[i][k] * acc[i][k] : 0.f;
+    for (int k = 0; k < 16; ++k) v += acc[i][k] * acc[i][k];
   v = wave_sum(v * s2);
   float* red = reinterpret_cast<float*>(smem);
   if (lane == 0) red[wv] = v;
   __syncthreads();
-  if (tid == 0) {
-    float sum = (red[0] + red[1]) + (red[2] + red[3]);
-    if constexpr (TG == 2) sum += (red[4] + red[5]) + (red[6] + red[7]);
-    partial[lid] = sum;
-  }
-}
-
-// tap groups of the direct3x3 kernels: one group of 4 waves (9 accumulators, one wave per
-// SIMD) by default; DD_D3_TG=2 takes the two-group form (5 / 4 accumulators, two waves per
-// SIMD), measured 0.76x at 32x32 and 0.90x on the persistent 16x16 kernel (in-process A/B,
-// profiles/r04_conv/ab_pegrad_tg2_rejected.txt): the second wave re-reads the B fragments and
-// the LDS traffic per MFMA rises, which costs more than the hidden latency gains
-static int d3_tap_groups() {
-  static int v = -1;
-  if (v < 0) {
-    const char* e = getenv("DD_D3_TG");
-    v = (e && e[0] == '2') ? 2 : 1;
-  }
-  return v;
-}
-
-template <int W, int STR, int TG>
-static void launch_direct3x3_tg(const float* act, const float* gout, int64_t B, int cin,
-                                int cout, int H, const float* col_scale, float* partial,
-                                hipStream_t st) {
-  using C = D3Cfg<W, STR>;
-  const int ncb = (int)ceil_div(cin, 64), nob = (int)ceil_div(cout, 64);
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pegrad_direct3x3_kernel<W, STR, TG>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    attr_set = true;
-  }
-  pegrad_direct3x3_kernel<W, STR, TG><<<(unsigned)(B * ncb * nob), 256 * TG, C::LDS, st>>>(
-      act, gout, cin, cout, H, ncb, nob, col_scale, partial);
+  if (tid == 0) partial[lid] = (red[0] + red[1]) + (red[2] + red[3]);
 }
 
 template <int W, int STR>
 static void launch_direct3x3(const float* act, const float* gout, int64_t B, int cin, int cout,
                              int H, const float* col_scale, float* partial, hipStream_t st) {
-  if (d3_tap_groups() == 1)
-    launch_direct3x3_tg<W, STR, 1>(act, gout, B, cin, cout, H, col_scale, partial, st);
-  else
-    launch_direct3x3_tg<W, STR, 2>(act, gout, B, cin, cout, H, col_scale, partial, st);
+  using C = D3Cfg<W, STR>;
+  const int ncb = (int)ceil_div(cin, 64), nob = (int)ceil_div(cout, 64);
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pegrad_direct3x3_kernel<W, STR>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
+    attr_set = true;
+  }
+  pegrad_direct3x3_kernel<W, STR><<<(unsigned)(B * ncb * nob), 256, C::LDS, st>>>(
+      act, gout, cin, cout, H, ncb, nob, col_scale, partial);
 }
 
 // Persistent where it pays (16-wide output maps: 8 steps per tile): one workgroup per CU walks
@@ -780,8 +739,8 @@ static void launch_direct3x3(const float* act, const float* gout, int64_t B, int
 // its conversion into LDS is exposed.  (The prologue was 9-15 % of a one-tile workgroup;
 // measured 1.04x at 16x16 and 1.06x on the 32 -> 16 head, 0.95x at 32x32 — 32 steps per
 // tile, where pegrad_direct3x3_kernel stays: one tile per workgroup.)
-template <int W, int STR, int TG>
-__global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3p_kernel(
+template <int W, int STR>
+__global__ __launch_bounds__(256, 1) void pegrad_direct3x3p_kernel(
     const float* __restrict__ act, const float* __restrict__ gout, int cin, int cout, int H,
     int n_cblk, int n_oblk, const float* __restrict__ col_scale, float* __restrict__ partial,
     int total) {
@@ -789,7 +748,7 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3p_kernel(
   extern __shared__ __attribute__((aligned(16))) char smem[];
   char* act_lds = smem;
   char* g_lds = smem + C::ACT_BYTES;
-  float* red = reinterpret_cast<float*>(smem + C::LDS);  // 4 TG floats past the staging
+  float* red = reinterpret_cast<float*>(smem + C::LDS);  // 4 floats past the staging
 
   const int per_ex = n_cblk * n_oblk;
   const int HW = H * W;                       // output positions
@@ -806,10 +765,9 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3p_kernel(
     g_b = gout + (size_t)b * cout * HW;
   };
 
-  constexpr int NTH = 256 * TG;
+  constexpr int NTH = 256;
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  const int wq = wv & 3, tg = __builtin_amdgcn_readfirstlane(wv >> 2);
-  const int wc = wq & 1, wo = wq >> 1, r = lane & 31, h = lane >> 5;
+  const int wc = wv & 1, wo = (wv >> 1) & 1, r = lane & 31, h = lane >> 5;  // 2 x 2 waves
 
   // ---- staging: 2 float4 of activations (one input row slice) + 2 float4 of gradients.
   // Loads are unconditional from clamped addresses and out-of-range values are zeroed when
@@ -819,8 +777,7 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3p_kernel(
   // WIN rows of a tile's first window)
   constexpr int NAW = C::WIN * 64 * C::WI / 4 / NTH;
   static_assert(C::WIN * 64 * C::WI / 4 % NTH == 0, "whole float4 rounds");
-  static_assert(C::NA % TG == 0, "whole staging rounds per tap group");
-  constexpr int NGT = 2 / TG;  // gradient float4 per thread
+  constexpr int NGT = 2;  // gradient float4 per thread
   float4 ra[NAW], rg[NGT];
   bool va[NAW], vg[NGT];
   auto load_rows = [&](auto NKc, int ir0, int nrows, int tstep) {
@@ -909,9 +866,9 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3p_kernel(
     }
   };
 
-  constexpr int NACC = TG == 1 ? 9 : 5;  // accumulators per wave: its tap group's taps
-  floatx16 acc[NACC];
-  const std::integral_constant<int, C::NA / TG> KN;
+  constexpr int NTAP = 9;  // one accumulator per tap
+  floatx16 acc[NTAP];
+  const std::integral_constant<int, C::NA> KN;
   const std::integral_constant<int, NAW> KW;
 
   const int nsteps = H / C::R;
@@ -948,26 +905,25 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3p_kernel(
       if (has_next) load_rows(KW, -1, C::WIN, 0);  // the tile vars already name the next tile
     }
     const int gbuf = st & 1;
-    auto group = [&](auto T0c, auto NTc) {
-      constexpr int T0 = decltype(T0c)::value, NTAP = decltype(NTc)::value;
+    {
       bf16x8 bh0, bl0, ah0[NTAP], al0[NTAP], bh1, bl1, ah1[NTAP], al1[NTAP];
       // only B and the first tap of sub-step 0 before its first MFMA; its other reads and
       // sub-step 1's B go two per MFMA gap behind the first NTAP MFMAs, then sub-step 1's A
       // reads one per gap, in this fixed order
       bh0 = frag(y0, gbuf, 0, -1, 0);
       bl0 = frag(y0, gbuf, 0, -1, 1);
-      ah0[0] = frag(y0, gbuf, 0, T0, 0);
-      al0[0] = frag(y0, gbuf, 0, T0, 1);
+      ah0[0] = frag(y0, gbuf, 0, 0, 0);
+      al0[0] = frag(y0, gbuf, 0, 0, 1);
       auto rd = [&](int j) {  // the j-th read behind the MFMAs
         constexpr int J0 = 2 * (NTAP - 1), J1 = J0 + 2, J2 = J1 + 2 * NTAP;
         if (j < J0) {
-          if (j & 1) al0[1 + j / 2] = frag(y0, gbuf, 0, T0 + 1 + j / 2, 1);
-          else ah0[1 + j / 2] = frag(y0, gbuf, 0, T0 + 1 + j / 2, 0);
+          if (j & 1) al0[1 + j / 2] = frag(y0, gbuf, 0, 1 + j / 2, 1);
+          else ah0[1 + j / 2] = frag(y0, gbuf, 0, 1 + j / 2, 0);
         } else if (j < J1) {
           (j == J0 ? bh1 : bl1) = frag(y0, gbuf, 1, -1, j - J0);
         } else if (j < J2) {
-          if ((j - J1) & 1) al1[(j - J1) / 2] = frag(y0, gbuf, 1, T0 + (j - J1) / 2, 1);
-          else ah1[(j - J1) / 2] = frag(y0, gbuf, 1, T0 + (j - J1) / 2, 0);
+          if ((j - J1) & 1) al1[(j - J1) / 2] = frag(y0, gbuf, 1, (j - J1) / 2, 1);
+          else ah1[(j - J1) / 2] = frag(y0, gbuf, 1, (j - J1) / 2, 0);
         }
       };
 #pragma unroll
@@ -1005,23 +961,13 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3p_kernel(
         __builtin_amdgcn_sched_group_barrier(0x008, 1, 1);
       }
       __builtin_amdgcn_sched_barrier(0);
-    };
-    using I0 = std::integral_constant<int, 0>;
-    using I5 = std::integral_constant<int, 5>;
-    if constexpr (TG == 1) {
-      group(I0{}, std::integral_constant<int, 9>{});
-    } else if (tg == 0) {
-      group(I0{}, I5{});
-    } else {
-      group(I5{}, std::integral_constant<int, 4>{});
     }
     __syncthreads();
   };
 
-  const int ntap = TG == 1 ? 9 : (tg == 0 ? 5 : 4);
   for (;;) {
 #pragma unroll
-    for (int i = 0; i < NACC; ++i) acc[i] = floatx16{0};
+    for (int i = 0; i < NTAP; ++i) acc[i] = floatx16{0};
     for (int st = 0; st + 1 < nsteps; ++st) step(st, std::false_type{}, false);
     // the last step: switch the tile variables to the next tile first (its window loads
     // issue under this step's MFMAs); this tile's output index and column scales are kept
@@ -1039,55 +985,39 @@ __global__ __launch_bounds__(256 * TG, 1) void pegrad_direct3x3p_kernel(
     }
     float v = 0.f;
 #pragma unroll
-    for (int i = 0; i < NACC; ++i)
+    for (int i = 0; i < NTAP; ++i)
 #pragma unroll
-      for (int k = 0; k < 16; ++k) v += i < ntap ? acc[i][k] * acc[i][k] : 0.f;
+      for (int k = 0; k < 16; ++k) v += acc[i][k] * acc[i][k];
     v = wave_sum(v * s2);
     if (lane == 0) red[wv] = v;
     // the next tile's window and step-0 gradients into LDS (every wave passed the last
     // step's barrier, so no slot is being read)
     if (has_next) store_rows(KW, -1, 0);
     __syncthreads();
-    if (tid == 0) {
-      float sum = (red[0] + red[1]) + (red[2] + red[3]);
-      if constexpr (TG == 2) sum += (red[4] + red[5]) + (red[6] + red[7]);
-      partial[lid_c] = sum;
-    }
+    if (tid == 0) partial[lid_c] = (red[0] + red[1]) + (red[2] + red[3]);
     if (!has_next) break;
     __syncthreads();  // red is rewritten by the next tile
     t = tn;
   }
 }
 
-template <int W, int STR, int TG>
-static void launch_direct3x3p_tg(const float* act, const float* gout, int64_t B, int cin,
-                                 int cout, int H, const float* col_scale, float* partial,
-                                 hipStream_t st) {
+template <int W, int STR>
+static void launch_direct3x3p(const float* act, const float* gout, int64_t B, int cin, int cout,
+                              int H, const float* col_scale, float* partial, hipStream_t st) {
   using C = D3Cfg<W, STR>;
   const int ncb = (int)ceil_div(cin, 64), nob = (int)ceil_div(cout, 64);
-  constexpr int LDS = C::LDS + 16 * TG;  // + the 4 TG partial sums
+  constexpr int LDS = C::LDS + 16;  // + the 4 partial sums
   static_assert(LDS <= 160 * 1024, "LDS budget");
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pegrad_direct3x3p_kernel<W, STR, TG>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pegrad_direct3x3p_kernel<W, STR>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
     attr_set = true;
   }
   const int64_t total = B * ncb * nob;
   const int64_t grid = std::min<int64_t>(total, device_cus());
-  pegrad_direct3x3p_kernel<W, STR, TG><<<(unsigned)grid, 256 * TG, LDS, st>>>(
+  pegrad_direct3x3p_kernel<W, STR><<<(unsigned)grid, 256, LDS, st>>>(
       act, gout, cin, cout, H, ncb, nob, col_scale, partial, (int)total);
-}
-
-template <int W, int STR>
-static void launch_direct3x3p(const float* act, const float* gout, int64_t B, int cin, int cout,
-                              int H, const float* col_scale, float* partial, hipStream_t st) {
-  // (the stride-2 head keeps one tap group: its 5-row next-tile window held in registers
-  // across the last step does not fit the 256 registers of two waves per SIMD -- 49 spilled)
-  if (d3_tap_groups() == 1 || STR == 2)
-    launch_direct3x3p_tg<W, STR, 1>(act, gout, B, cin, cout, H, col_scale, partial, st);
-  else
-    launch_direct3x3p_tg<W, STR, 2>(act, gout, B, cin, cout, H, col_scale, partial, st);
 }
 
 static bool direct3x3_ok(const dd_conv_geom* g) {

@@ -636,7 +636,7 @@ static bool probe_once(int dev) {
 // "match" in $DD_SELECT_RANK forces the ballot-match rank (read once; no device work)
 static int force_match_rank() {
   static const int v = [] {
-    const char* e = getenv("DD_SELECT_RANK");
+    const char* e = env_str("DD_SELECT_RANK");
     return (e && e[0] == 'm') ? 1 : 0;
   }();
   return v;

@@ -381,6 +381,33 @@ def test_pgram_q_is_deterministic(cuda):
     assert all(torch.equal(o, outs[0]) for o in outs)
 
 
+def test_pgram_q_ignores_ablation_env(cuda, monkeypatch):
+    """pgram_q has one build: a stray DD_PGQ_ABL in a job's environment (once the switch of
+    builds that skipped the MFMAs, the gather or the loads) changes no score.  19 examples: two
+    workgroup rows of 8 and a ragged tail, at the smallest channel counts of PGQ."""
+    act, gout, k, s, p = _conv_case(cuda, (19, 17, 16, 16, 33, 3, 1, 1), 5)
+    ref = o_pegrad.conv_pegrad_sqnorm(act, gout, k, k, s, p)
+    a, g = torch.from_numpy(act).to(cuda), torch.from_numpy(gout).to(cuda)
+    geom = _capi.conv_geom(a, g, (k, k), s, p)
+    assert _capi.conv_method(geom, "ghost", "bf16x3") == "pgram_q"
+    ws = torch.empty(_capi.conv_workspace_bytes(geom, "ghost", "bf16x3"), dtype=torch.uint8,
+                     device=cuda)
+
+    def run():
+        sq = torch.zeros(19, device=cuda)
+        _capi.conv_pegrad_sqnorm(a, g, (k, k), s, p, sq, ws, method="ghost", precision="bf16x3")
+        return sq.cpu()
+
+    monkeypatch.delenv("DD_PGQ_ABL", raising=False)
+    clean = run()
+    monkeypatch.setenv("DD_PGQ_ABL", "15")
+    stray = run()
+    assert torch.equal(clean, stray)
+    for out in (clean, stray):
+        np.testing.assert_allclose(out.numpy().astype(np.float64), ref, rtol=1e-4,
+                                   atol=1e-7 * max(1.0, ref.max()))
+
+
 # ---- BN affine per-example gradient norm (grand_params: all) ----------------------------------
 @pytest.mark.parametrize("B,C,H,W,res", [(5, 64, 32, 32, False), (3, 128, 16, 16, True),
                                          (4, 256, 8, 8, False), (6, 512, 4, 4, True),

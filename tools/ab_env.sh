@@ -2,7 +2,7 @@
 # Interleaved A/B of one environment knob on tools/conv_micro.py (same build, one process per
 # run, rounds alternate so box drift cancels):
 #   tools/ab_env.sh <out> <rounds> <only> <VAR> <value> [<value> ...]
-# e.g. tools/ab_env.sh gpurun_out/stag 2 conv DD_CONV_STAGGER 0 4000 8000
+# e.g. tools/ab_env.sh out/xcd 2 conv DD_CONV_XCD 0 1
 set -uo pipefail
 OUT=$1; ROUNDS=$2; ONLY=$3; VAR=$4; shift 4
 mkdir -p "$OUT"

@@ -5,7 +5,7 @@ export TMPDIR=/tmp PYTHONUNBUFFERED=1
 OUT=gpurun_out/${1:-r06kj}
 mkdir -p "$OUT"
 i=0
-for cfg in "base" "DD_CONV_STAGGER=2000" "DD_DOWN_WA=2" "DD_CONV_TILE=narrow" "base" "DD_CONV_STAGGER=2000"; do
+for cfg in "base" "DD_DOWN_WA=2" "base" "DD_DOWN_WA=2"; do
   i=$((i+1))
   if [ "$cfg" = "base" ]; then envs=(); else envs=($cfg); fi
   env "${envs[@]}" timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 --full --no-cpu-baseline \

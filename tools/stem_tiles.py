@@ -1,6 +1,7 @@
-"""Time the stem conv (3 -> 64, 32x32, 1024 examples) through libdd under the current
-DD_CONV_TILE family: plain, GraNd-forward (bias + ReLU + mask_out) and EL2N (stats) epilogues.
-    DD_CONV_TILE=wide python tools/stem_tiles.py"""
+"""Time the stem conv (3 -> 64, 32x32, 1024 examples) through libdd (DD_LIB picks the build):
+plain, GraNd-forward (bias + ReLU + mask_out) and EL2N (stats) epilogues; the optional argument
+tags the output lines.
+    DD_LIB=build/exp/libdd.so python tools/stem_tiles.py exp"""
 import os
 import sys
 
@@ -32,7 +33,7 @@ def main():
     bias = torch.randn(cout, device=dev, generator=g)
     mo = _capi.conv3x3_mask(B, cout, H, H, dev)
     fl = 2.0 * B * H * H * cin * cout * 9
-    tag = os.environ.get("DD_CONV_TILE", "default")
+    tag = sys.argv[1] if len(sys.argv) > 1 else "default"
     for name, fn in (
             ("plain", lambda: _capi.conv3x3(x, pk, cout)),
             ("bias+relu+mask_out", lambda: _capi.conv3x3(x, pk, cout, bias=bias, relu=True,
