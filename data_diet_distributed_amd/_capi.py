@@ -43,6 +43,7 @@ EXPORTS = (
     "dd_conv3x3_mask_plane_bits", "dd_conv3x3_unit_input_supported",
     "dd_conv3x3_forward_unit_input", "dd_down_forward_unit_input",
     "dd_conv1x1_forward_unit_input",
+    "dd_class_counts", "dd_select_by_class_workspace_bytes", "dd_select_topk_by_class",
 )
 
 
@@ -100,6 +101,10 @@ def lib():
                 "dd_keep_count": (I64, [I64, F64]),
                 "dd_select_workspace_bytes": (SZ, [I64]),
                 "dd_select_topk": (I32, [P, I64, I64, P, P, P, P, SZ, P]),
+                "dd_class_counts": (I32, [P, I64, I64, P, P, P]),
+                "dd_select_by_class_workspace_bytes": (SZ, [I64, I64]),
+                "dd_select_topk_by_class": (I32, [P, P, I64, I64, P, P, I64, P, P, P, P, SZ,
+                                                  P]),
                 "dd_conv3x3_pack_bytes": (SZ, [I32, I32]),
                 "dd_conv3x3_pack": (I32, [P, I32, I32, I32, I32, F32, P, P]),
                 "dd_conv3x3_tiles_per_group": (I32, [I32, I32, I32]),
@@ -503,6 +508,101 @@ def select_topk(keys: torch.Tensor, k: int, idx_out=None, workspace=None, check_
         if c != 0:
             raise ValueError(f"{c} NaN score(s): the keep-set is undefined")
     return idx_out, thr, nan
+
+
+# ---- selection with per-class quotas -----------------------------------------------------------
+def class_counts(labels: torch.Tensor, num_classes: int, check: bool = True):
+    """Members per class of int64 labels [n] -> (counts int64 [C], bad int32 [1]) on device;
+    bad = labels outside [0, C), which count into no class.  With check it is read back (one
+    sync) and a bad label raises LabelError."""
+    _dev(labels, torch.int64, "labels", 1)
+    C = int(num_classes)
+    if C < 1:
+        raise ValueError("num_classes must be positive")
+    counts = torch.empty(C, dtype=torch.int64, device=labels.device)
+    bad = torch.empty(1, dtype=torch.int32, device=labels.device)
+    rc = lib().dd_class_counts(_dev(labels, torch.int64, "labels"), labels.numel(), C,
+                               _dev(counts, torch.int64, "counts"),
+                               _dev(bad, torch.int32, "bad"), _stream(labels))
+    _check(rc, "dd_class_counts")
+    if check:
+        check_labels(bad, C, "class_counts")
+    return counts, bad
+
+
+def select_by_class_workspace_bytes(n: int, num_classes: int) -> int:
+    return int(lib().dd_select_by_class_workspace_bytes(int(n), int(num_classes)))
+
+
+def _class_vector(v, C, name, dev):
+    if not isinstance(v, torch.Tensor):
+        v = torch.tensor([int(x) for x in v], dtype=torch.int64)
+    if v.device != dev:
+        v = v.to(dev)
+    _dev(v, torch.int64, name, 1)
+    if v.numel() != C:
+        raise ValueError(f"{name} must have one entry per class ({C}), got {v.numel()}")
+    return v
+
+
+def select_topk_by_class(keys: torch.Tensor, labels: torch.Tensor, num_classes: int, skip, quota,
+                         k_total: int = None, idx_out=None, workspace=None, check=True):
+    """Class c keeps its members at in-class ranks [skip[c], skip[c] + quota[c]) (key
+    descending, ties by ascending index); returns every kept index in select_topk's global
+    order.  skip / quota: int64 [C] device tensors, or host sequences (copied to the device;
+    k_total then defaults to sum(quota)).
+
+    Returns (idx int64[k_total], nan_count int32[1], err int32[1]) on device.  With check, one
+    read-back raises ValueError on a NaN key, LabelError on a label outside [0, C) and
+    ValueError on a class whose window exceeds its size (or quotas that do not sum to
+    k_total); check=False enqueues only (graph capture) and leaves the counts to the caller."""
+    _dev(keys, torch.float32, "keys", 1)
+    _dev(labels, torch.int64, "labels", 1)
+    n, C, dev = keys.numel(), int(num_classes), keys.device
+    if labels.numel() != n or labels.device != dev:
+        raise ValueError("labels must have one entry per key, on the keys' device")
+    if k_total is None:
+        if isinstance(quota, torch.Tensor):
+            raise ValueError("k_total is required with a device quota tensor")
+        k_total = sum(int(q) for q in quota)
+    k_total = int(k_total)
+    if not 0 <= k_total <= n:
+        raise ValueError(f"k_total={k_total} outside [0, {n}]")
+    skip = _class_vector(skip, C, "skip", dev)
+    quota = _class_vector(quota, C, "quota", dev)
+    need = select_by_class_workspace_bytes(n, C)
+    if need == 0:
+        raise ValueError(f"select_topk_by_class: unsupported size n={n}, num_classes={C}")
+    if idx_out is None:
+        idx_out = torch.empty(k_total, dtype=torch.int64, device=dev)
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    stat = torch.empty(3, dtype=torch.int32, device=dev)  # NaN keys, err, bad labels
+    e0 = _t0(keys, always=True)
+    rc = lib().dd_select_topk_by_class(
+        _dev(keys, torch.float32, "keys"), _dev(labels, torch.int64, "labels"), n, C,
+        _dev(skip, torch.int64, "skip"), _dev(quota, torch.int64, "quota"), k_total,
+        _opt(idx_out, torch.int64, "idx_out", k_total), ctypes.c_void_p(stat.data_ptr()),
+        ctypes.c_void_p(stat.data_ptr() + 4), ctypes.c_void_p(workspace.data_ptr()),
+        workspace.numel() * workspace.element_size(), _stream(keys))
+    _check(rc, "dd_select_topk_by_class")
+    _t1(e0, "select", 12.0 * n + 8.0 * k_total, keys)  # keys + int64 labels once + int64 idx
+    if check:
+        # err does not tell a bad label from a bad window: count the bad labels on their own
+        counts = torch.empty(C, dtype=torch.int64, device=dev)
+        rc = lib().dd_class_counts(_dev(labels, torch.int64, "labels"), n, C,
+                                   _dev(counts, torch.int64, "counts"),
+                                   ctypes.c_void_p(stat.data_ptr() + 8), _stream(keys))
+        _check(rc, "dd_class_counts")
+        nan, err, bad = (int(v) for v in stat.tolist())
+        if nan:
+            raise ValueError(f"{nan} NaN score(s): the keep-set is undefined")
+        if bad:
+            raise LabelError(f"select_topk_by_class: {bad} label(s) outside [0, {C})")
+        if err:
+            raise ValueError("select_topk_by_class: a class's skip + quota exceeds its size, "
+                             "or the quotas do not sum to k_total")
+    return idx_out, stat[0:1], stat[1:2]
 
 
 # ---- operand halves of the split MFMA convs (include/dd_capi.h DD_OPERANDS_*) -----------------

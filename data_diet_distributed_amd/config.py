@@ -16,6 +16,8 @@ REFERENCE_KEYS = ("device", "sparse", "sparsity", "batch_size_scores", "num_work
 DEFAULTS = {
     "score_methods": ["el2n"],        # el2n and/or grand
     "select_by": "el2n",
+    "select_policy": "global",        # global (reference) | stratified | balanced class quotas
+    "select_skip": 0,                 # ranks skipped from the top before the k kept ones
     "score_checkpoints": 1,           # K (seed{k}/ckpt_{epoch}.pth when K > 1)
     "score_epoch": 19,
     "bn_mode": "batch",               # EL2N BN: batch (reference) | running (eval)

@@ -43,13 +43,15 @@ from .subset_index import write_subset_index
 from .synthetic import state_digest
 
 
-def el2n_scores_from_loader(train_loader, net, device, num_classes=None):
+def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect=None):
     """Scores of every example the loader yields, in visit order, plus the visited indices.
+    A dict given as `collect` receives "labels" (the targets in visit order, int64 on the
+    device) and "num_classes" (the width of the logits), for the class selection policies.
 
     Runs `net(input)` exactly as the reference does (:15), so BN follows `net.training`
     (train mode for a freshly built net, as in train.py:59-63).  A label outside [0, C)
     raises LabelError, as the reference's one_hot does (:17)."""
-    scores, visit = [], []
+    scores, visit, targets = [], [], []
     bad = _capi.label_counter(device)
     C = None
     with torch.no_grad():
@@ -63,7 +65,13 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None):
             C = out.shape[1]
             _capi.el2n(out, target.contiguous(), score=s, bad_labels=bad)
             scores.append(s)
+            if collect is not None:
+                targets.append(target.flatten())
             visit.append(torch.as_tensor(idx).to(out.device, non_blocking=True))
+    if collect is not None:
+        collect["labels"] = (torch.cat(targets) if targets
+                             else torch.empty(0, dtype=torch.int64, device=device))
+        collect["num_classes"] = C
     if not scores:
         return (torch.empty(0, dtype=torch.float32, device=device),
                 torch.empty(0, dtype=torch.int64, device=device))
@@ -354,16 +362,28 @@ def refine_fast_keep_set(train_loader, src, model, device, scores, visit, sample
 
 def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size, num_workers,
                   *, dataset=None, subset_index_path=None, return_indices=False,
-                  fast: bool = True, refine="auto"):
+                  fast: bool = True, refine="auto", policy="global", skip=0):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
     refine=True re-scores the fast path's near-threshold visit batches in plain fp32
     (refine_fast_keep_set; `sparse_loader.last_refine` records what it did); "auto" (default)
     and False keep the fast path's keep-set as it is: its forward runs on fp16 halves, whose
-    scores are fp32-grade (ScoreConfig.refine)."""
-    from .scoring import normalize_refine
+    scores are fp32-grade (ScoreConfig.refine).
+    policy / skip: which examples are kept (ScoreConfig.select_policy / select_skip):
+    "global" with skip 0 is the reference's rule; "stratified" / "balanced" keep per-class
+    quotas (scoring.apportion over the class counts of the visited examples), skip > 0 leaves
+    out that many of the top-ranked first.  Ties, also within a class, keep visit order;
+    `sparse_loader.last_selection` records the quotas.  refine=True needs the default rule."""
+    from .scoring import SELECT_POLICIES, normalize_refine, select_with_policy
     refine = normalize_refine(refine)
+    if policy not in SELECT_POLICIES:
+        raise ValueError(f"policy must be one of {SELECT_POLICIES} (got {policy!r})")
+    if isinstance(skip, bool) or not isinstance(skip, (int, np.integer)) or skip < 0:
+        raise ValueError(f"skip must be an integer >= 0 (got {skip!r})")
+    default_rule = policy == "global" and skip == 0
+    if refine is True and not default_rule:
+        raise ValueError("refine=True needs the default selection (policy='global', skip=0)")
     if torch.device(device).type != "cuda":
         raise ValueError("sparse_loader runs its kernels on a GPU device (libdd.so)")
     module = net.module if hasattr(net, "module") else net
@@ -375,12 +395,25 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     if fp is not None:
         scores, visit = el2n_scores_fast(train_loader, fp[0], fp[1], device)
     else:
-        scores, visit = el2n_scores_from_loader(train_loader, net, device)
+        seen = None if policy == "global" else {}  # a class policy needs the visited targets
+        scores, visit = el2n_scores_from_loader(train_loader, net, device, collect=seen)
     samples = _capi.keep_count(train_samples, sparsity)
     if samples < 0 or samples > scores.numel():
         raise ValueError(f"keep count {samples} outside [0, {scores.numel()}]")
     sparse_loader.last_refine = None
-    if fp is not None and refine is True and 0 < samples < scores.numel():
+    sparse_loader.last_selection = None
+    if not default_rule:
+        if policy == "global":
+            labels_visit = ncls = None
+        elif fp is not None:  # the labels of the raw source, in visit order
+            labels_visit = torch.from_numpy(fp[0][2]).to(scores.device)[visit]
+            ncls = fp[1].linear.out_features
+        else:
+            labels_visit, ncls = seen["labels"], seen["num_classes"] or 1
+        pos, sparse_loader.last_selection = select_with_policy(
+            scores.contiguous(), labels_visit, ncls, samples, policy, int(skip))
+        kept = visit[pos]
+    elif fp is not None and refine is True and 0 < samples < scores.numel():
         pos, sparse_loader.last_refine = refine_fast_keep_set(
             train_loader, fp[0], fp[1], device, scores, visit, samples)
         kept = visit[pos]
@@ -401,7 +434,11 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                                                        "out_features", 0)) or None,
                             "bn_mode": "train" if module.training else "eval",
                             "order": "loader visit order (reference semantics)",
-                            "checkpoint_digests": [digest]})
+                            "checkpoint_digests": [digest],
+                            **({} if default_rule else {
+                                "select_policy": policy, "select_skip": int(skip),
+                                "class_quota": sparse_loader.last_selection["class_quota"],
+                                "class_skip": sparse_loader.last_selection["class_skip"]})})
     sparse_train_loader = DataLoader(train_subset, batch_size=batch_size, shuffle=True,
                                      num_workers=num_workers)
     if return_indices:

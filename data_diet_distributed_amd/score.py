@@ -11,6 +11,8 @@ rest (config.DEFAULTS):
 
   score_methods      el2n and/or grand               select_by     ranking score
   score_checkpoints  K: checkpoint_path/seed{k}/ckpt_{score_epoch}.pth (K = 1: ckpt_E.pth)
+  select_policy      global (reference) | stratified | balanced: per-class quotas (--policy)
+  select_skip        ranks skipped from the top before the kept window (--skip)
   bn_mode            EL2N BatchNorm: batch|train (reference) or running|eval
   pegrad_method      auto | direct | ghost             grand_batch   GraNd chunk
   score_gpus         ranks (one per GPU; self-launched here, or run under torchrun)
@@ -127,6 +129,8 @@ def engine_config(cfg):
                        pegrad_method=cfg.get("pegrad_method", "auto"),
                        lanes=int(cfg.get("score_lanes", 3)),
                        refine_max_frac=float(cfg.get("refine_max_frac", 0.08)),
+                       select_policy=str(cfg.get("select_policy", "global")),
+                       select_skip=int(cfg.get("select_skip", 0)),
                        **SCORE_PRECISIONS[prec])
 
 
@@ -174,6 +178,10 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
                 "grand_batch": ecfg.grand_batch, "world_size": world,
                 "order": "score descending, ties by ascending index (pinned batch partition)",
                 "seconds": secs, "examples_per_s": n / secs if secs > 0 else None}
+        sel = eng.last_selection
+        if sel["policy"] != "global" or sel["skip"]:  # (a default run's metadata is unchanged)
+            meta.update(select_policy=sel["policy"], select_skip=sel["skip"],
+                        class_quota=sel["class_quota"], class_skip=sel["class_skip"])
         out_path = out_path or cfg.get("subset_index_path")
         if out_path:
             path = write_subset_index(out_path, kept_np, meta)
@@ -194,12 +202,20 @@ def parse(argv=None):
     ap.add_argument("--out", default=None, help="index artefact path (default: "
                                                  "subset_index_path of the config)")
     ap.add_argument("--gpus", type=int, default=None, help="ranks (default: score_gpus)")
+    ap.add_argument("--policy", default=None, choices=("global", "stratified", "balanced"),
+                    help="keep-set rule (default: select_policy of the config)")
+    ap.add_argument("--skip", type=int, default=None,
+                    help="ranks skipped from the top (default: select_skip of the config)")
     return ap.parse_args(argv)
 
 
 def main(argv=None):
     args = parse(argv)
     cfg = config_mod.load_config(args.config)
+    if args.policy is not None:
+        cfg["select_policy"] = args.policy
+    if args.skip is not None:
+        cfg["select_skip"] = args.skip
     gpus = args.gpus or int(cfg.get("score_gpus", 1))
     if gpus > 1 and not launch.under_launcher():
         rest = list(sys.argv[1:] if argv is None else argv)

@@ -15,6 +15,8 @@ device-resident pipeline:
     dd_ensemble_finalize (mean over K)
   RCCL all-gather of the fp32 score vectors (the one collective)
   dd_select_topk on the full vector -> keep indices (reference :22-24 order and tie rule)
+  (ScoreConfig.select_policy / select_skip: per-class quotas and offset windows instead, on
+  dd_class_counts + dd_select_topk_by_class: select_with_policy)
 
 Parity protocol: batch b = global indices [b*B, (b+1)*B), unshuffled, so
 train-mode-BN EL2N scores are identical for any number of ranks.
@@ -98,6 +100,17 @@ class ScoreConfig:
     refine_max_frac: float = 0.08
     refine_min_sample: int = 512             # rows in the first re-scored sample, at least
     refine_groups: int = 8                   # pinned batches per fp32 EL2N launch
+    # Which examples the keep-set takes (k = dd_keep_count as ever):
+    #   "global"      the reference's rule: global ranks [select_skip, select_skip + k)
+    #   "stratified"  per-class quotas in proportion to the class sizes (apportion)
+    #   "balanced"    equal per-class quotas, water-filled where a class is too small
+    # With a class policy, select_skip is apportioned over the classes by the same rule and
+    # class c keeps its in-class ranks [s_c, s_c + q_c) (select_with_policy).  The refinement
+    # re-scores around ONE threshold, so it applies to the default selection only: with a
+    # class policy or select_skip > 0, refine=True is rejected and "auto" behaves as False
+    # (last_refine stays None).
+    select_policy: str = "global"
+    select_skip: int = 0
 
     def __post_init__(self):
         self.methods = tuple(self.methods)
@@ -125,9 +138,103 @@ class ScoreConfig:
         if (self.refine_rel < 0 or self.refine_tol <= 0 or self.refine_groups < 1
                 or not 0 < self.refine_max_frac <= 1):
             raise ValueError("refine_rel >= 0, refine_tol > 0, refine_groups >= 1")
+        if self.select_policy not in SELECT_POLICIES:
+            raise ValueError(f"select_policy must be one of {SELECT_POLICIES} "
+                             f"(got {self.select_policy!r})")
+        if (isinstance(self.select_skip, bool)
+                or not isinstance(self.select_skip, (int, np.integer)) or self.select_skip < 0):
+            raise ValueError(f"select_skip must be an integer >= 0 (got {self.select_skip!r})")
+        self.select_skip = int(self.select_skip)
+        if self.refine is True and not self.default_selection():
+            raise ValueError("refine=True needs the default selection (select_policy='global', "
+                             "select_skip=0): the refinement re-scores around one threshold")
         if self.el2n_chunk < self.batch_size:
             self.el2n_chunk = self.batch_size
         self.el2n_chunk -= self.el2n_chunk % self.batch_size
+
+    def default_selection(self) -> bool:
+        return self.select_policy == "global" and self.select_skip == 0
+
+
+SELECT_POLICIES = ("global", "stratified", "balanced")
+
+
+def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
+    """Split `total` units over classes with capacities `caps`: a[c] with sum(a) == total and
+    0 <= a[c] <= caps[c] (needs total <= sum(caps)); exact integer arithmetic.
+
+    "stratified": in proportion to the capacities, a[c] = total * caps[c] // M (M = sum(caps));
+      the units left over go one each to the largest remainders total * caps[c] % M, ties to
+      the lower class (a class with a remainder has room: total <= M).
+    "balanced": equal shares, water-filled: a[c] = min(caps[c], L) for the largest level L
+      with sum(a) <= total; the units left over go one each to the classes above L, in
+      ascending class order."""
+    total = int(total)
+    caps = [int(c) for c in caps]
+    if rule not in ("stratified", "balanced"):
+        raise ValueError(f"apportion rule must be 'stratified' or 'balanced' (got {rule!r})")
+    if total < 0 or any(c < 0 for c in caps):
+        raise ValueError("apportion: total and capacities must be >= 0")
+    M = sum(caps)
+    if total > M:
+        raise ValueError(f"apportion: total {total} exceeds the capacity {M}")
+    if total == M:
+        return caps
+    if rule == "stratified":
+        a = [total * c // M for c in caps]
+        by_rem = sorted(range(len(caps)), key=lambda c: (-(total * caps[c] % M), c))
+        for c in by_rem[:total - sum(a)]:
+            a[c] += 1
+        return a
+    lo, hi = 0, max(caps)  # the largest L in [lo, hi] with sum(min(caps, L)) <= total
+    while lo < hi:
+        mid = (lo + hi + 1) // 2
+        if sum(min(c, mid) for c in caps) <= total:
+            lo = mid
+        else:
+            hi = mid - 1
+    a = [min(c, lo) for c in caps]
+    left = total - sum(a)
+    for c in range(len(caps)):
+        if left and caps[c] > lo:
+            a[c] += 1
+            left -= 1
+    return a
+
+
+def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: str = "global",
+                       skip: int = 0, check_nan: bool = True):
+    """The keep-set of `k` of the n = keys.numel() examples under a selection policy
+    (ScoreConfig.select_policy / select_skip), in dd_select_topk's order: key descending, ties
+    by ascending index.  `labels` (int64 [n], on the keys' device) and `num_classes` are read
+    by the class policies only.
+
+    A class policy costs one small device -> host read (the class counts, from which
+    `apportion` makes the per-class skips s and quotas q = apportion(k, n_c - s)) before
+    dd_select_topk_by_class runs.  Returns (kept int64 [k] on device, record): the record is
+    {"policy", "skip", "class_counts", "class_skip", "class_quota"} (None x 3 for "global")."""
+    if policy not in SELECT_POLICIES:
+        raise ValueError(f"select policy must be one of {SELECT_POLICIES} (got {policy!r})")
+    n, k, skip = keys.numel(), int(k), int(skip)
+    if skip < 0 or k < 0 or skip + k > n:
+        raise ValueError(f"skip {skip} + keep count {k} outside [0, {n}]")
+    rec = {"policy": policy, "skip": skip, "class_counts": None, "class_skip": None,
+           "class_quota": None}
+    if policy == "global":
+        kept = _capi.select_topk(keys, skip + k, check_nan=check_nan)[0]
+        return (kept[skip:] if skip else kept), rec
+    C = int(num_classes)
+    labels = labels.contiguous()
+    counts, bad = _capi.class_counts(labels, C, check=False)
+    host = torch.cat([counts, bad.to(torch.int64)]).tolist()  # the one read of the counts
+    if host[C]:
+        raise _capi.LabelError(f"select: {host[C]} label(s) outside [0, {C})")
+    n_c = host[:C]
+    s = apportion(skip, n_c, policy)
+    q = apportion(k, [a - b for a, b in zip(n_c, s)], policy)
+    kept = _capi.select_topk_by_class(keys, labels, C, s, q, k_total=k, check=check_nan)[0]
+    rec.update(class_counts=n_c, class_skip=s, class_quota=q)
+    return kept, rec
 
 
 def normalize_refine(v) -> Union[bool, str]:
@@ -430,6 +537,9 @@ class ScoringEngine:
                 check_bn_gammas(m)
         self._wss: Dict[int, torch.Tensor] = {}  # pegrad workspace per lane
         self.last_refine: Optional[dict] = None  # what the last run()'s _refine did
+        # the last run()'s selection: {"policy", "skip", "class_counts", "class_skip",
+        # "class_quota"} (select_with_policy's record)
+        self.last_selection: Optional[dict] = None
         # set when a GraNd forward on fp16 operand halves overflowed and the engine re-scored
         # on bf16 halves (run(); the engine keeps bf16 GraNd packs from then on)
         self.grand_fallback: Optional[str] = None
@@ -797,7 +907,19 @@ class ScoringEngine:
             return self.score_shard(images_u8, labels, 0, hi - lo, check=False)
 
         def select(keys, k):
-            return _capi.select_topk(keys, k, check_nan=check_nan)[0]
+            c = self.cfg
+            if c.default_selection():
+                self.last_selection = {"policy": "global", "skip": 0, "class_counts": None,
+                                       "class_skip": None, "class_quota": None}
+                return _capi.select_topk(keys, k, check_nan=check_nan)[0]
+            all_labels = labels
+            if c.select_policy != "global" and n_total is not None:
+                # each rank holds its shard's labels: the class policies' one extra collective
+                all_labels = gather_scores(labels.contiguous(), N, B, group)
+            kept, self.last_selection = select_with_policy(
+                keys, all_labels, self.models[0].linear.out_features, k, c.select_policy,
+                c.select_skip, check_nan)
+            return kept
 
         full, kept, k = sharded_job(score, N, B, sparsity, self.cfg.select_by, select,
                                     _capi.keep_count, group,
@@ -813,7 +935,7 @@ class ScoringEngine:
         """Whether `method`'s near-threshold scores are re-computed in plain fp32
         (ScoreConfig.refine: forced, or "auto" where the pass carries bf16-halves arithmetic)."""
         c = self.cfg
-        if c.refine is False:
+        if c.refine is False or not c.default_selection():
             return False
         if method == "el2n":
             if c.refine == "auto" and c.el2n_operands == "f16x3":

@@ -520,6 +520,47 @@ int dd_select_topk(const float* keys, int64_t n, int64_t k, int64_t* idx_out, fl
                    int32_t* nan_count_out, void* workspace, size_t workspace_bytes,
                    void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Keep-set selection with per-class quotas (absent from the reference, whose only rule is the
+ * global top-k above).  Purely additive: no existing signature or result changes, so
+ * dd_abi_version() stays 10.
+ *
+ * Within class c (labels[i] == c) the members are ranked by key descending, ties by ascending
+ * index, NaN below every number (+0.0 == -0.0): dd_select_topk's order restricted to the class.
+ * Class c keeps the members at in-class ranks [skip[c], skip[c] + quota[c]).
+ *
+ * dd_class_counts: labels int64 [n]; counts_out int64 [num_classes] (device) = members per
+ *   class; bad_label_out int32 [1] (device) = labels outside [0, num_classes), which count
+ *   into no class.  Both are cleared first.  Integer atomics only; n < 2^31.
+ *
+ * dd_select_topk_by_class: keys fp32 [n], labels int64 [n], skip / quota int64 [num_classes]
+ *   (device), k_total = sum of the quotas, in [0, n].  Writes
+ *   idx_out int64 [k_total] : every kept index, ordered by key descending and ties by ascending
+ *                       index over the whole set (the order dd_select_topk gives); never
+ *                       written past k_total entries;
+ *   nan_count_out int32 [1] (device, NULL allowed): number of NaN keys;
+ *   err_out int32 [1] (device): labels outside [0, num_classes) + classes with skip < 0,
+ *                       quota < 0 or skip + quota above the class's size + 1 if the kept
+ *                       entries do not number k_total.  Non-zero: idx_out is unspecified.  The
+ *                       host wrapper reads it after the call and raises (no sync inside).
+ * The full stable order comes from dd_select_topk with k = n; a stable counting pass over the
+ * class ids along that order gives every entry its in-class rank (per-block class histograms,
+ * a scan over blocks, an in-tile rank), and a stable compaction of the entries inside their
+ * class's window writes idx_out.  n < 2^31, num_classes <= 2^20.  Workspace:
+ * dd_select_by_class_workspace_bytes(n, num_classes) (0 for unsupported sizes), 16-byte
+ * aligned; its per-call state is cleared on the stream: reusable across calls and graph replays.
+ * ---------------------------------------------------------------------------------------- */
+int dd_class_counts(const int64_t* labels, int64_t n, int64_t num_classes, int64_t* counts_out,
+                    int32_t* bad_label_out, void* stream);
+
+size_t dd_select_by_class_workspace_bytes(int64_t n, int64_t num_classes);
+
+int dd_select_topk_by_class(const float* keys, const int64_t* labels, int64_t n,
+                            int64_t num_classes, const int64_t* skip, const int64_t* quota,
+                            int64_t k_total, int64_t* idx_out, int32_t* nan_count_out,
+                            int32_t* err_out, void* workspace, size_t workspace_bytes,
+                            void* stream);
+
 #ifdef __cplusplus
 }
 #endif
