@@ -44,6 +44,7 @@ EXPORTS = (
     "dd_conv3x3_forward_unit_input", "dd_down_forward_unit_input",
     "dd_conv1x1_forward_unit_input",
     "dd_class_counts", "dd_select_by_class_workspace_bytes", "dd_select_topk_by_class",
+    "dd_logit_scores", "dd_variability_finalize",
 )
 
 
@@ -90,6 +91,8 @@ def lib():
                 "dd_synth_images_u8": (I32, [ctypes.c_uint64, I64, I64, I32, I32, I32, I32, P,
                                              P, P]),
                 "dd_el2n": (I32, [P, P, I64, I32, P, P, P, P, P]),
+                "dd_logit_scores": (I32, [P, P, I64, I32, P, P, P, P, P, P, P, I32, P, P]),
+                "dd_variability_finalize": (I32, [P, I64, I32, P, P]),
                 "dd_conv_pegrad_method": (I32, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_workspace_bytes": (SZ, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_sqnorm": (I32, [P, P, ctypes.POINTER(ConvGeom), P, I32, I32, P,
@@ -327,6 +330,50 @@ def el2n(logits: torch.Tensor, labels: torch.Tensor, score=None, e=None, accum=N
     _t1(e0, "el2n", B * (4 * C + 8 + (4 if score is not None else 0) +
                          (4 * C if e is not None else 0) + (8 if accum is not None else 0)),
         logits)
+
+
+# the single-forward statistics dd_logit_scores accumulates (keyword = statistic name)
+LOGIT_STATS = ("loss", "margin", "entropy", "error", "wrong_mass")
+
+
+def logit_scores(logits: torch.Tensor, labels: torch.Tensor, *, loss=None, margin=None,
+                 entropy=None, error=None, wrong_mass=None, var_mean=None, var_m2=None,
+                 k: int = 0, bad_labels=None):
+    """The logit scores beside EL2N, from one read of the logits (dd_logit_scores; the formulas
+    and NaN rules are in include/dd_capi.h).  Each keyword given is an fp32 [B] accumulator:
+    accum[b] += the row's statistic.  var_mean / var_m2 (both or neither) take Welford's
+    update of wrong_mass for the 1-based checkpoint ordinal `k`; variability_finalize turns
+    M2 into the standard deviation.  bad_labels: as el2n()."""
+    _dev(logits, torch.float32, "logits", 2)
+    B, C = logits.shape
+    if labels.numel() != B:
+        raise ValueError("labels must have B entries")
+    if (var_mean is None) != (var_m2 is None):
+        raise ValueError("var_mean and var_m2 go together")
+    accs = (loss, margin, entropy, error, wrong_mass, var_mean, var_m2)
+    names = LOGIT_STATS + ("var_mean", "var_m2")
+    if all(a is None for a in accs):
+        raise ValueError("logit_scores: no statistic requested")
+    ptrs = [_opt(a, torch.float32, n, B) for a, n in zip(accs, names)]
+    if B == 0:  # nothing to do (and an empty tensor's pointer is NULL: "not requested")
+        return
+    e0 = _t0(logits)
+    rc = lib().dd_logit_scores(
+        _dev(logits, torch.float32, "logits"), _dev(labels, torch.int64, "labels"), B, C,
+        *ptrs, int(k),
+        _opt(bad_labels, torch.int32, "bad_labels", 1), _stream(logits))
+    _check(rc, "dd_logit_scores")
+    # logits + int64 label + each accumulator read and written
+    _t1(e0, "el2n", B * (4 * C + 8 + 8 * sum(a is not None for a in accs)), logits)
+
+
+def variability_finalize(m2: torch.Tensor, K: int, out: torch.Tensor):
+    """out = sqrt(M2 / K): the population standard deviation of the Welford pair."""
+    if m2.numel() != out.numel():
+        raise ValueError("size mismatch")
+    rc = lib().dd_variability_finalize(_dev(m2, torch.float32, "m2"), m2.numel(), int(K),
+                                       _dev(out, torch.float32, "out"), _stream(m2))
+    _check(rc, "dd_variability_finalize")
 
 
 def label_counter(device) -> torch.Tensor:

@@ -43,8 +43,20 @@ from .subset_index import write_subset_index
 from .synthetic import state_digest
 
 
-def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect=None):
-    """Scores of every example the loader yields, in visit order, plus the visited indices.
+def _score_rows(logits, labels, out, bad, score="el2n"):
+    """out[b] = the chosen score of each row of one launch's logits: EL2N (dd_el2n), or one of
+    the single-forward logit statistics (dd_logit_scores accumulating into zeros)."""
+    if score == "el2n":
+        _capi.el2n(logits, labels, score=out, bad_labels=bad)
+    else:
+        out.zero_()
+        _capi.logit_scores(logits, labels, bad_labels=bad, **{score: out})
+
+
+def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect=None,
+                            score="el2n"):
+    """Scores of every example the loader yields, in visit order, plus the visited indices
+    (`score`: "el2n" or one of _capi.LOGIT_STATS, from the same logits).
     A dict given as `collect` receives "labels" (the targets in visit order, int64 on the
     device) and "num_classes" (the width of the logits), for the class selection policies.
 
@@ -63,7 +75,7 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
                 raise ValueError(f"net produces {out.shape[1]} classes, expected {num_classes}")
             s = torch.empty(out.shape[0], dtype=torch.float32, device=out.device)
             C = out.shape[1]
-            _capi.el2n(out, target.contiguous(), score=s, bad_labels=bad)
+            _score_rows(out, target.contiguous(), s, bad, score)
             scores.append(s)
             if collect is not None:
                 targets.append(target.flatten())
@@ -268,7 +280,7 @@ def fast_path(train_loader, net, device):
     return src, model
 
 
-def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024):
+def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, score="el2n"):
     """Scores in visit order + visited indices, like el2n_scores_from_loader, on the hand
     kernels: every visit batch of the loader's BatchSampler (all of size B but a ragged last
     one) is one BN group; chunks of whole batches are gathered + normalised on device."""
@@ -305,7 +317,7 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024):
             idx = visit_d[c0:c1]
             _capi.normalize_u8(img_d, mean, std, xb[:rows], index=idx)
             logits = el2n_fast.forward_logits(model, xb, B, rows)[:rows]
-            _capi.el2n(logits.contiguous(), lab_d[idx], score=scores[c0:c1], bad_labels=bad)
+            _score_rows(logits.contiguous(), lab_d[idx], scores[c0:c1], bad, score)
     # a label outside [0, C): the reference's one_hot raises (:17), so does this path
     _capi.check_labels(bad, model.linear.out_features, "sparse_loader")
     return scores, visit_d
@@ -362,7 +374,7 @@ def refine_fast_keep_set(train_loader, src, model, device, scores, visit, sample
 
 def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size, num_workers,
                   *, dataset=None, subset_index_path=None, return_indices=False,
-                  fast: bool = True, refine="auto", policy="global", skip=0):
+                  fast: bool = True, refine="auto", policy="global", skip=0, score="el2n"):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
@@ -374,9 +386,21 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     "global" with skip 0 is the reference's rule; "stratified" / "balanced" keep per-class
     quotas (scoring.apportion over the class counts of the visited examples), skip > 0 leaves
     out that many of the top-ranked first.  Ties, also within a class, keep visit order;
-    `sparse_loader.last_selection` records the quotas.  refine=True needs the default rule."""
+    `sparse_loader.last_selection` records the quotas.  refine=True needs the default rule.
+    score: what ranks the examples: "el2n" (the reference's score), or one of the other
+    single-forward logit scores "loss", "margin", "entropy", "error", "wrong_mass"
+    (dd_logit_scores on the same logits; larger = harder, so policy / skip apply unchanged).
+    "variability" and "grand" need K checkpoints / a backward pass: the engine
+    (scoring.ScoringEngine) computes them.  refine=True needs score="el2n"."""
     from .scoring import SELECT_POLICIES, normalize_refine, select_with_policy
     refine = normalize_refine(refine)
+    if score in ("variability", "grand"):
+        raise ValueError(f"score={score!r} is computed by the scoring engine "
+                         f"(scoring.ScoringEngine / score.py), not by sparse_loader")
+    if score != "el2n" and score not in _capi.LOGIT_STATS:
+        raise ValueError(f"score must be 'el2n' or one of {_capi.LOGIT_STATS} (got {score!r})")
+    if refine is True and score != "el2n":
+        raise ValueError("refine=True re-scores EL2N only: it needs score='el2n'")
     if policy not in SELECT_POLICIES:
         raise ValueError(f"policy must be one of {SELECT_POLICIES} (got {policy!r})")
     if isinstance(skip, bool) or not isinstance(skip, (int, np.integer)) or skip < 0:
@@ -393,10 +417,11 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     fp = fast_path(train_loader, net, device) if fast else None
     sparse_loader.last_path = "fast" if fp is not None else "general"
     if fp is not None:
-        scores, visit = el2n_scores_fast(train_loader, fp[0], fp[1], device)
+        scores, visit = el2n_scores_fast(train_loader, fp[0], fp[1], device, score=score)
     else:
         seen = None if policy == "global" else {}  # a class policy needs the visited targets
-        scores, visit = el2n_scores_from_loader(train_loader, net, device, collect=seen)
+        scores, visit = el2n_scores_from_loader(train_loader, net, device, collect=seen,
+                                                score=score)
     samples = _capi.keep_count(train_samples, sparsity)
     if samples < 0 or samples > scores.numel():
         raise ValueError(f"keep count {samples} outside [0, {scores.numel()}]")
@@ -428,7 +453,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     if subset_index_path:
         write_subset_index(subset_index_path, indices,
                            {"n": int(train_samples), "sparsity": float(sparsity),
-                            "score_methods": ["el2n"], "select_by": "el2n", "K": 1,
+                            "score_methods": [score], "select_by": score, "K": 1,
                             "arch": type(module).__name__,
                             "num_classes": int(getattr(getattr(module, "linear", None),
                                                        "out_features", 0)) or None,

@@ -7,7 +7,9 @@ device-resident pipeline:
     for each of K checkpoints
       EL2N  : uint8 -> normalised fp32 (dd_normalize_u8) -> ResNet forward with batch-stat BN
               over the pinned partition [b*B, (b+1)*B) (MIOpen) -> dd_el2n accumulates into the
-              ensemble buffer (no per-example host syncs; reference :19-20 did 2 per example)
+              ensemble buffer (no per-example host syncs; reference :19-20 did 2 per example);
+              the other logit scores (LOGIT_METHODS: loss, margin, entropy, error, wrong_mass,
+              variability) come from the same logits, one dd_logit_scores launch beside it
       GraNd : eval-BN forward with a tape of Conv2d/Linear (input, output) -> dd_el2n emits the
               residual e = d(sum CE)/d(logits) -> autograd back to every conv output only
               (weights frozen: no weight-gradient GEMMs) -> dd_conv_pegrad_sqnorm per conv
@@ -40,7 +42,10 @@ STD = (0.2023, 0.1994, 0.2010)
 
 @dataclasses.dataclass
 class ScoreConfig:
-    methods: Sequence[str] = ("el2n",)      # subset of {"el2n", "grand"}
+    # subset of {"el2n", "grand"} + LOGIT_METHODS (loss, margin, entropy, error, wrong_mass,
+    # variability: the other scores of the EL2N forward, dd_logit_scores; the whole logit
+    # family shares one forward per checkpoint)
+    methods: Sequence[str] = ("el2n",)
     select_by: str = "el2n"                  # which ensemble score ranks the keep-set
     batch_size: int = 128                    # EL2N batch partition (config.yaml:7 batch_size)
     el2n_bn: str = "batch"                   # "batch" = reference semantics; "running" = eval
@@ -115,7 +120,7 @@ class ScoreConfig:
     def __post_init__(self):
         self.methods = tuple(self.methods)
         for m in self.methods:
-            if m not in ("el2n", "grand"):
+            if m not in ("el2n", "grand") + LOGIT_METHODS:
                 raise ValueError(f"unknown score method {m!r}")
         if self.select_by not in self.methods:
             raise ValueError(f"select_by={self.select_by!r} not among methods {self.methods}")
@@ -148,6 +153,9 @@ class ScoreConfig:
         if self.refine is True and not self.default_selection():
             raise ValueError("refine=True needs the default selection (select_policy='global', "
                              "select_skip=0): the refinement re-scores around one threshold")
+        if self.refine is True and self.select_by in LOGIT_METHODS:
+            raise ValueError(f"refine=True re-scores EL2N or GraNd only (select_by="
+                             f"{self.select_by!r})")
         if self.el2n_chunk < self.batch_size:
             self.el2n_chunk = self.batch_size
         self.el2n_chunk -= self.el2n_chunk % self.batch_size
@@ -157,6 +165,17 @@ class ScoreConfig:
 
 
 SELECT_POLICIES = ("global", "stratified", "balanced")
+
+# The logit scores beside EL2N (include/dd_capi.h dd_logit_scores): the mean over the K
+# checkpoints of the five single-forward statistics, and Dataset Cartography's variability, the
+# standard deviation of wrong_mass over the checkpoints.  Larger means harder for every one.
+LOGIT_METHODS = _capi.LOGIT_STATS + ("variability",)
+LOGIT_FAMILY = ("el2n",) + LOGIT_METHODS  # the scores of one train-BN forward per checkpoint
+
+
+def pass_of(method: str) -> str:
+    """The pass that computes `method`: "el2n" (the logit family's shared forward) or "grand"."""
+    return "el2n" if method in LOGIT_FAMILY else "grand"
 
 
 def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
@@ -515,6 +534,9 @@ class ScoringEngine:
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("the scoring engine runs on a GPU (libdd.so has no CPU path)")
+        if cfg.select_by == "variability" and len(models) < 2:
+            raise ValueError("select_by='variability' needs at least two checkpoints: the "
+                             "standard deviation over one checkpoint is 0 for every example")
         _capi.lib()  # fail loudly now if the HIP library is missing
         # per-checkpoint setup cost (bench.py reports it beside the steady-state step)
         self.setup_times = {"fold_s_per_ckpt": 0.0, "pack_s_per_ckpt": 0.0}
@@ -580,8 +602,30 @@ class ScoringEngine:
             self.progress(f"{what} chunk {ci + 1}/{n}")
 
     # ---- passes ----------------------------------------------------------------------------
+    def _score_logits(self, model: ResNet, logits, labels, accum, r0, r1):
+        """One launch's logits into rows [r0, r1) of the logit family's accumulators.  `accum`
+        is the EL2N accumulator (a tensor), or {method: accumulator} over the requested family
+        members ("variability" holds Welford's M2 and "variability_mean" its mean): dd_el2n
+        runs only if el2n is among them, and one dd_logit_scores launch serves all the others.
+        The label counter of the pass goes to dd_el2n when it runs, else to dd_logit_scores,
+        so a row is counted once."""
+        if isinstance(accum, torch.Tensor):
+            accum = {"el2n": accum}
+        counter = self._counter("el2n", model)
+        if "el2n" in accum:
+            _capi.el2n(logits, labels, accum=accum["el2n"][r0:r1], bad_labels=counter)
+            counter = None
+        kw = {m: accum[m][r0:r1] for m in _capi.LOGIT_STATS if m in accum}
+        if "variability" in accum:
+            kw.update(var_mean=accum["variability_mean"][r0:r1],
+                      var_m2=accum["variability"][r0:r1],
+                      k=1 + next(i for i, m in enumerate(self.models) if m is model))
+        if kw:
+            _capi.logit_scores(logits, labels, bad_labels=counter, **kw)
+
     def el2n_pass(self, model: ResNet, images_u8, labels, lo, hi, accum):
-        """accum[j] += EL2N(x_{lo+j}) for the shard, batch partition anchored at 0.
+        """accum[j] += EL2N(x_{lo+j}) for the shard, batch partition anchored at 0 (accum: the
+        EL2N accumulator, or the logit family's accumulators: _score_logits).
 
         A ragged final batch (N % B rows) is run padded to B rows with its BN statistics
         taken over the valid rows only (`n_valid`): identical scores, and MIOpen keeps the
@@ -605,8 +649,7 @@ class ScoringEngine:
                 logits = model.run(x, bn=self.cfg.el2n_bn, n_valid=n if pad else None,
                                    fast=self.cfg.fast_convs)
                 logits = logits[:n].float().contiguous()
-                _capi.el2n(logits, labels[b0:b1], accum=accum[b0 - lo:b1 - lo],
-                           bad_labels=self._counter("el2n", model))
+                self._score_logits(model, logits, labels[b0:b1], accum, b0 - lo, b1 - lo)
 
     def _el2n_pass_grouped(self, model: ResNet, images_u8, labels, lo, hi, accum):
         """el2n_pass on the hand-scheduled forward: `el2n_chunk` examples (whole pinned BN
@@ -638,8 +681,7 @@ class ScoringEngine:
                     xb[n:].zero_()
                 self._normalize(images_u8[b0:b1], xb[:n])
                 logits = el2n_fast.forward_logits(model, xb, B, n)[:n]
-                _capi.el2n(logits, labels[b0:b1], accum=accum[b0 - lo:b1 - lo],
-                           bad_labels=self._counter("el2n", model))
+                self._score_logits(model, logits, labels[b0:b1], accum, b0 - lo, b1 - lo)
             yield
 
     def grand_pass(self, model: ResNet, images_u8, labels, lo, hi, accum):
@@ -726,7 +768,7 @@ class ScoringEngine:
     def _lanes_apply(self) -> bool:
         """Lanes interleave the chunk generators of the hand-scheduled passes."""
         c = self.cfg
-        el2n_ok = "el2n" not in c.methods or (
+        el2n_ok = not any(m in LOGIT_FAMILY for m in c.methods) or (
             c.fast_el2n and c.fast_convs and c.el2n_bn == "batch"
             and all(el2n_fast.applicable(m) for m in self.models))
         return el2n_ok
@@ -744,16 +786,24 @@ class ScoringEngine:
         self._bad = _capi.label_counter(self.device)
         # counted on the first pass over the shard only (the first method's first checkpoint
         # scores every row once), so the count is of rows, not of row-passes
-        self._bad_pass = (self.cfg.methods[0], self.models[0])
+        self._bad_pass = (pass_of(self.cfg.methods[0]), self.models[0])
         accs = {m: torch.zeros(n, dtype=torch.float32, device=self.device)
                 for m in self.cfg.methods}
+        # the logit family (el2n + LOGIT_METHODS) shares one forward per checkpoint and chunk:
+        # its pass takes all the requested members' accumulators at once (_score_logits)
+        family = {m: accs[m] for m in self.cfg.methods if m in LOGIT_FAMILY}
+        if "variability" in family:  # accs["variability"] is Welford's M2, this is its mean
+            family["variability_mean"] = torch.zeros_like(accs["variability"])
+        kinds = list(dict.fromkeys(pass_of(m) for m in self.cfg.methods))  # first-use order
+        targets = {"el2n": family, "grand": accs.get("grand")}
+        buffers = {"el2n": list(family.values()), "grand": [accs.get("grand")]}
 
-        def passes(method):
+        def passes(kind):
             for model in self.models:
-                if method == "el2n":
-                    self.el2n_pass(model, images_u8, labels, lo, hi, accs[method])
+                if kind == "el2n":
+                    self.el2n_pass(model, images_u8, labels, lo, hi, family)
                 else:
-                    self.grand_pass(model, images_u8, labels, lo, hi, accs[method])
+                    self.grand_pass(model, images_u8, labels, lo, hi, accs["grand"])
 
         lanes = self.cfg.lanes
         if lanes > 1 and self._lanes_apply():
@@ -763,10 +813,10 @@ class ScoringEngine:
             streams = self._lane_streams[:lanes]
             for st in streams:
                 st.wait_stream(main)  # inputs and accumulators are ready on the main stream
-            for method in self.cfg.methods:
-                gen = self._el2n_chunks if method == "el2n" else self._grand_chunks
+            for kind in kinds:
+                gen = self._el2n_chunks if kind == "el2n" else self._grand_chunks
                 for model in self.models:
-                    its = [gen(model, images_u8, labels, lo, hi, accs[method], lane=j,
+                    its = [gen(model, images_u8, labels, lo, hi, targets[kind], lane=j,
                                lanes=lanes) for j in range(lanes)]
                     live = list(range(lanes))
                     while live:  # one chunk per lane in turn, each on its lane's stream
@@ -775,28 +825,33 @@ class ScoringEngine:
                                 if next(its[j], StopIteration) is StopIteration:
                                     live.remove(j)
             for st in streams:
-                for acc in accs.values():
-                    acc.record_stream(st)
+                for kind in kinds:
+                    for acc in buffers[kind]:
+                        acc.record_stream(st)
                 main.wait_stream(st)
-        elif self.cfg.concurrent_passes and len(self.cfg.methods) > 1:
+        elif self.cfg.concurrent_passes and len(kinds) > 1:
             main = torch.cuda.current_stream(self.device)
             if self._side is None:
                 self._side = torch.cuda.Stream(self.device)
             side = self._side
             side.wait_stream(main)  # inputs and accumulators are ready on the main stream
             with torch.cuda.stream(side):
-                passes(self.cfg.methods[0])
-            accs[self.cfg.methods[0]].record_stream(side)
-            for m in self.cfg.methods[1:]:
-                passes(m)
+                passes(kinds[0])
+            for acc in buffers[kinds[0]]:
+                acc.record_stream(side)
+            for kind in kinds[1:]:
+                passes(kind)
             main.wait_stream(side)
         else:
-            for m in self.cfg.methods:
-                passes(m)
+            for kind in kinds:
+                passes(kind)
         out = {}
         for method in self.cfg.methods:
             res = torch.empty_like(accs[method])
-            _capi.ensemble_finalize(accs[method], K, res)
+            if method == "variability":
+                _capi.variability_finalize(accs[method], K, res)
+            else:
+                _capi.ensemble_finalize(accs[method], K, res)
             out[method] = res
         if check and n:
             _capi.check_labels(self._bad, self.models[0].linear.out_features, "score_shard")
@@ -806,7 +861,7 @@ class ScoringEngine:
                     # e.g. an activation past fp16's range (65504) in a forward on fp16 operand
                     # halves: fail loudly rather than return non-finite scores (run() re-scores
                     # on bf16 halves by itself)
-                    ops = "el2n_operands" if m == "el2n" else "grand_operands"
+                    ops = "el2n_operands" if m in LOGIT_FAMILY else "grand_operands"
                     raise ValueError(f"non-finite {m} scores" + (
                         f": an activation of the forward may have left fp16's range; score "
                         f"with {ops}='bf16x3' (ScoreConfig), or through run(), which falls "
@@ -833,7 +888,9 @@ class ScoringEngine:
                                              shard and gathers again; the engine keeps the bf16
                                              packs (`fallback` records it; EL2N on bf16 halves
                                              then takes the near-threshold fp32 re-scoring,
-                                             refine "auto");
+                                             refine "auto"); the logit family shares its
+                                             forward, so one non-finite member re-scores
+                                             every requested member;
           anything else non-finite        -> ValueError (the selection would reject NaN)."""
         ms = list(full)
         if not ms or N == 0:
@@ -846,17 +903,25 @@ class ScoringEngine:
             _all_reduce_sum(bad, group)
         _capi.check_labels(bad, self.models[0].linear.out_features, "run")
         redo = [m for i, m in enumerate(ms) if not bool(fin[i]) and self._f16_forward(m)]
+        if any(m in LOGIT_FAMILY for m in redo):
+            # the logit family shares its forward: the whole requested family is re-scored, in
+            # one forward per checkpoint again
+            redo = [m for m in ms if m in LOGIT_FAMILY or m in redo]
         if redo:
             ops = {"el2n": "el2n_operands", "grand": "grand_operands"}
-            self.cfg = dataclasses.replace(self.cfg, **{ops[m]: "bf16x3" for m in redo})
-            self.fallback = {m: "a forward activation left fp16's range: re-scored on bf16 "
-                                "operand halves" for m in redo}
+            self.cfg = dataclasses.replace(self.cfg,
+                                           **{ops[pass_of(m)]: "bf16x3" for m in redo})
+            self.fallback.update({m: "a forward activation left fp16's range: re-scored on "
+                                     "bf16 operand halves" for m in redo})
             if "grand" in redo:
                 self.grand_fallback = self.fallback["grand"]
             for mod in self.models:
                 mod.prepare_fast_convs(self.cfg.el2n_operands, self.cfg.grand_operands)
             saved = self.cfg
-            self.cfg = dataclasses.replace(saved, methods=tuple(redo), select_by=redo[0])
+            # (refine=False: the re-scoring pass does not refine, and refine=True would reject
+            # a select_by among the logit scores)
+            self.cfg = dataclasses.replace(saved, methods=tuple(redo), select_by=redo[0],
+                                           refine=False)
             try:
                 world, rank = _world(group)
                 lo, hi = shard_bounds(N, B, world, rank)
@@ -877,7 +942,7 @@ class ScoringEngine:
         c = self.cfg
         if not c.fast_convs:
             return False
-        if method == "el2n":
+        if method in LOGIT_FAMILY:  # one forward for the whole family
             return c.el2n_operands == "f16x3"
         return c.grand_operands == "f16x3" and c.fold_bn
 
@@ -936,6 +1001,8 @@ class ScoringEngine:
         (ScoreConfig.refine: forced, or "auto" where the pass carries bf16-halves arithmetic)."""
         c = self.cfg
         if c.refine is False or not c.default_selection():
+            return False
+        if method in LOGIT_METHODS:  # the refinement re-scores EL2N and GraNd only
             return False
         if method == "el2n":
             if c.refine == "auto" and c.el2n_operands == "f16x3":

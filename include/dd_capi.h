@@ -102,6 +102,47 @@ int dd_el2n(const float* logits, const int64_t* labels, int64_t B, int32_t C,
             float* score, float* e, float* accum, int32_t* bad_labels, void* stream);
 
 /* ---------------------------------------------------------------------------------------- *
+ * The other logit scores of the same forward (absent from the reference, which keeps EL2N
+ * only): one launch, one read of the logits, any subset.  Purely additive: no existing
+ * signature or result changes, so dd_abi_version() stays 10.
+ *
+ * Per row: logits z[0..C), label y, m = max_j z_j, e_j = exp(z_j - m), s = sum_j e_j.  Every
+ * statistic is oriented so that larger means harder:
+ *   loss        (m - z_y) + log s             cross-entropy as log-sum-exp, never -log(p_y)
+ *   margin      max_{j != y} z_j - z_y        one fp32 subtraction (the quantity behind AUM)
+ *   entropy     log s - (sum_j e_j (z_j - m)) / s     a term with e_j == 0 contributes 0
+ *   error       1.0 if max_{j != y} z_j >= z_y else 0.0   (a tie with the label is an error)
+ *   wrong_mass  (sum_{j != y} e_j) / s        1 - p_y without the cancellation (as dd_el2n's
+ *                                             e_y); one minus the Cartography confidence
+ * logits fp32 [B, C] row-major, labels int64 [B].  Outputs, each fp32 [B] and each may be NULL
+ * (a statistic that is not asked for costs no store):
+ *   loss_accum, margin_accum, entropy_accum, error_accum, wrong_mass_accum:
+ *       accum[b] += the row's statistic (the K-checkpoint running sum; dd_ensemble_finalize
+ *       makes the mean);
+ *   var_mean, var_m2 (both or neither) with the 1-based checkpoint ordinal k: Welford's update
+ *       of w = wrong_mass over the checkpoints, in checkpoint order 1..K,
+ *           mean_k = mean_{k-1} + (w - mean_{k-1}) / k,   M2 += (w - mean_{k-1}) (w - mean_k)
+ *       (k == 1 writes mean = w, M2 = 0 without reading the buffers);
+ *       dd_variability_finalize then gives the population standard deviation
+ *       out[i] = sqrt(max(M2[i], 0) / K) (NaN stays NaN), Dataset Cartography's variability.
+ *   bad_labels int32 [1] (device): += the number of rows whose label lies outside [0, C).
+ * NaN rules: a row with a label outside [0, C) (dd_el2n's rule: counted once, one integer
+ * atomic add), or with a NaN or +inf logit, gives NaN in every requested statistic and
+ * accumulator term (-inf logits are unspecified).
+ * margin / error need C >= 2.  B == 0 returns DD_OK; nothing requested, C < 1, B < 0, NULL
+ * logits / labels with B > 0, one pointer of the Welford pair without the other, or the pair
+ * with k < 1 are DD_EINVAL before any launch.
+ * A row's results depend on that row alone and are reduced in an order fixed by C (no float
+ * atomics): bitwise independent of B, of the row's position and of the buffers' alignment.
+ * No synchronisation inside (graph-capturable).
+ * ---------------------------------------------------------------------------------------- */
+int dd_logit_scores(const float* logits, const int64_t* labels, int64_t B, int32_t C,
+                    float* loss_accum, float* margin_accum, float* entropy_accum,
+                    float* error_accum, float* wrong_mass_accum, float* var_mean, float* var_m2,
+                    int32_t k, int32_t* bad_labels, void* stream);
+int dd_variability_finalize(const float* m2, int64_t n, int32_t K, float* out, void* stream);
+
+/* ---------------------------------------------------------------------------------------- *
  * GraNd per-example gradient norms (north star (b); absent from the reference, which scores
  * with EL2N only — get_scores_and_prune.py:15-18; layers hooked: models/resnet.py:12-18,
  * 22-23, 40-47, 52-53, 71, 78).
