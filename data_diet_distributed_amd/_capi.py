@@ -45,6 +45,7 @@ EXPORTS = (
     "dd_conv1x1_forward_unit_input",
     "dd_class_counts", "dd_select_by_class_workspace_bytes", "dd_select_topk_by_class",
     "dd_logit_scores", "dd_variability_finalize",
+    "dd_class_feature_sums", "dd_class_centroids", "dd_proto_scores",
 )
 
 
@@ -93,6 +94,9 @@ def lib():
                 "dd_el2n": (I32, [P, P, I64, I32, P, P, P, P, P]),
                 "dd_logit_scores": (I32, [P, P, I64, I32, P, P, P, P, P, P, P, I32, P, P]),
                 "dd_variability_finalize": (I32, [P, I64, I32, P, P]),
+                "dd_class_feature_sums": (I32, [P, P, P, I64, I32, I64, P, P, P]),
+                "dd_class_centroids": (I32, [P, P, P, I64, I32, P, P]),
+                "dd_proto_scores": (I32, [P, P, P, I64, I32, I64, P, P, P]),
                 "dd_conv_pegrad_method": (I32, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_workspace_bytes": (SZ, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_sqnorm": (I32, [P, P, ctypes.POINTER(ConvGeom), P, I32, I32, P,
@@ -374,6 +378,78 @@ def variability_finalize(m2: torch.Tensor, K: int, out: torch.Tensor):
     rc = lib().dd_variability_finalize(_dev(m2, torch.float32, "m2"), m2.numel(), int(K),
                                        _dev(out, torch.float32, "out"), _stream(m2))
     _check(rc, "dd_variability_finalize")
+
+
+# ---- distance to the class prototype -----------------------------------------------------------
+PROTO_MAX_D = 4096           # dd_linear_forward's bound
+PROTO_MAX_CLASS = 1 << 24    # members per class the int64 fixed-point sums hold without overflow
+
+
+def class_feature_sums(feat: torch.Tensor, labels: torch.Tensor, sums: torch.Tensor,
+                       bad_feat: torch.Tensor, order: torch.Tensor = None):
+    """sums[y_i] += the rows of feat [n, D] in 2^-24 fixed point (dd_class_feature_sums: exact
+    int64 sums, identical for any split, order or launch geometry).  sums int64 [C, D] and
+    bad_feat int32 [C] accumulate: the caller clears them.  order: int64 [n], the rows
+    stable-sorted by label (fewer atomics), or None."""
+    _dev(feat, torch.float32, "feat", 2)
+    n, D = feat.shape
+    _dev(sums, torch.int64, "sums", 2)
+    C = sums.shape[0]
+    if sums.shape[1] != D:
+        raise ValueError(f"sums must be [C, {D}] (got {tuple(sums.shape)})")
+    if labels.numel() != n:
+        raise ValueError("labels must have n entries")
+    e0 = _t0(feat, always=True)
+    rc = lib().dd_class_feature_sums(
+        _dev(feat, torch.float32, "feat"), _dev(labels, torch.int64, "labels", 1),
+        _opt(order, torch.int64, "order", n), n, D, C, _dev(sums, torch.int64, "sums"),
+        _opt(bad_feat, torch.int32, "bad_feat", C), _stream(feat))
+    _check(rc, "dd_class_feature_sums")
+    # the rows + label + order entry read once (the atomics' traffic is not algorithmic)
+    _t1(e0, "el2n", n * (4.0 * D + 8 + (8 if order is not None else 0)), feat)
+
+
+def class_centroids(sums: torch.Tensor, counts: torch.Tensor, bad_feat: torch.Tensor,
+                    out: torch.Tensor = None) -> torch.Tensor:
+    """fp32 [C, D] centroids of the fixed-point sums (dd_class_centroids): 0 for an empty class,
+    NaN for a class with bad_feat != 0."""
+    _dev(sums, torch.int64, "sums", 2)
+    C, D = sums.shape
+    if out is None:
+        out = torch.empty((C, D), dtype=torch.float32, device=sums.device)
+    rc = lib().dd_class_centroids(_dev(sums, torch.int64, "sums"),
+                                  _opt(counts, torch.int64, "counts", C),
+                                  _opt(bad_feat, torch.int32, "bad_feat", C), C, D,
+                                  _opt(out, torch.float32, "centroids", C * D), _stream(sums))
+    _check(rc, "dd_class_centroids")
+    return out
+
+
+def proto_scores(feat: torch.Tensor, labels: torch.Tensor, centroids: torch.Tensor, score=None,
+                 accum=None):
+    """score[b] = ||feat[b] - centroids[labels[b]]||_2 and / or accum[b] += it
+    (dd_proto_scores; NaN for a label outside [0, C) or a non-finite feature)."""
+    _dev(feat, torch.float32, "feat", 2)
+    B, D = feat.shape
+    _dev(centroids, torch.float32, "centroids", 2)
+    C = centroids.shape[0]
+    if centroids.shape[1] != D:
+        raise ValueError(f"centroids must be [C, {D}] (got {tuple(centroids.shape)})")
+    if labels.numel() != B:
+        raise ValueError("labels must have B entries")
+    if score is None and accum is None:
+        raise ValueError("proto_scores: no output requested")
+    ptrs = [_opt(score, torch.float32, "score", B), _opt(accum, torch.float32, "accum", B)]
+    if B == 0:  # nothing to do (and an empty tensor's pointer is NULL: "not requested")
+        return
+    e0 = _t0(feat, always=True)
+    rc = lib().dd_proto_scores(_dev(feat, torch.float32, "feat"),
+                               _dev(labels, torch.int64, "labels", 1),
+                               _dev(centroids, torch.float32, "centroids"), B, D, C, *ptrs,
+                               _stream(feat))
+    _check(rc, "dd_proto_scores")
+    _t1(e0, "el2n", B * (4.0 * D + 8 + (4 if score is not None else 0) +
+                         (8 if accum is not None else 0)), feat)
 
 
 def label_counter(device) -> torch.Tensor:

@@ -15,7 +15,8 @@ REFERENCE_KEYS = ("device", "sparse", "sparsity", "batch_size_scores", "num_work
 # build extensions (defaults reproduce the reference: EL2N, one checkpoint ckpt_19, train BN)
 DEFAULTS = {
     # el2n and/or grand and/or the other logit scores of the EL2N forward: loss | margin |
-    # entropy | error | wrong_mass | variability (scoring.LOGIT_METHODS; select_by takes any)
+    # entropy | error | wrong_mass | variability (scoring.LOGIT_METHODS) | proto (the distance
+    # to the class prototype in feature space, scoring.FEATURE_METHODS); select_by takes any
     "score_methods": ["el2n"],
     "select_by": "el2n",
     "select_policy": "global",        # global (reference) | stratified | balanced class quotas

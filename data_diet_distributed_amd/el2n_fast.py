@@ -163,10 +163,22 @@ def _poolable(hw: int) -> bool:
     return hw % 4 == 0 and L >= 1 and L <= 64 and (L & (L - 1)) == 0
 
 
-@torch.inference_mode()
 def forward_logits(model: ResNet, x: torch.Tensor, group_size: int, n_valid: int) -> torch.Tensor:
     """Logits [B, C] of the train-mode-BN forward of x [B, 3, H, W] (contiguous fp32), with
     BN statistics per group of `group_size` rows over rows < n_valid."""
+    return forward_features(model, x, group_size, n_valid)[0]
+
+
+@torch.inference_mode()
+def forward_features(model: ResNet, x: torch.Tensor, group_size: int, n_valid: int):
+    """(logits [B, C], feat [B, D]) of the same forward: `feat` is the pooled fp32 row the
+    classifier consumes (contiguous; the feature-space scores read it).  Rows >= n_valid are
+    padding: their logits and features mean nothing.
+
+    A feature row depends on its BN group alone: it comes from the fused 4x4 pool of the unit
+    tail (dd_bn_apply, one fixed-order mean per (row, channel)) or, for the ImageNet stem and
+    maps that are not 4x4, from torch's average pool, which reduces each (row, channel) window
+    by itself; tests/test_gpu_proto_engine.py holds both bitwise across chunk sizes."""
     gs = int(group_size)
     y, aff = _conv_bn_stats(model, model.conv1, model.bn1, x, None, gs, n_valid)
     # `pending` = (y, (scale, shift), residual, residual affine): a unit output relu(bn(y) + R)
@@ -269,8 +281,9 @@ def forward_logits(model: ResNet, x: torch.Tensor, group_size: int, n_valid: int
         feat = out.reshape(out.size(0), -1)
     # per-row fixed-order classifier (dd_linear_forward): logits independent of the chunk size
     lin = model.linear
-    return _capi.linear_forward(feat.float().contiguous(), lin.weight.detach(),
-                                None if lin.bias is None else lin.bias.detach())
+    feat = feat.float().contiguous()
+    return _capi.linear_forward(feat, lin.weight.detach(),
+                                None if lin.bias is None else lin.bias.detach()), feat
 
 
 @torch.inference_mode()

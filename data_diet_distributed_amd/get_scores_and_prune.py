@@ -390,11 +390,12 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     score: what ranks the examples: "el2n" (the reference's score), or one of the other
     single-forward logit scores "loss", "margin", "entropy", "error", "wrong_mass"
     (dd_logit_scores on the same logits; larger = harder, so policy / skip apply unchanged).
-    "variability" and "grand" need K checkpoints / a backward pass: the engine
-    (scoring.ScoringEngine) computes them.  refine=True needs score="el2n"."""
+    "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
+    over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
+    score="el2n"."""
     from .scoring import SELECT_POLICIES, normalize_refine, select_with_policy
     refine = normalize_refine(refine)
-    if score in ("variability", "grand"):
+    if score in ("variability", "grand", "proto"):
         raise ValueError(f"score={score!r} is computed by the scoring engine "
                          f"(scoring.ScoringEngine / score.py), not by sparse_loader")
     if score != "el2n" and score not in _capi.LOGIT_STATS:

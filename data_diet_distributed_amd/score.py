@@ -12,7 +12,8 @@ rest (config.DEFAULTS):
   score_methods      el2n and/or grand               select_by     ranking score
                      and/or the other logit scores of the EL2N forward (one forward per
                      checkpoint for all of them): loss | margin | entropy | error |
-                     wrong_mass | variability (needs K >= 2 to rank by)
+                     wrong_mass | variability (needs K >= 2 to rank by), and proto (the
+                     distance of the pooled feature row to its class mean, same forward)
   score_checkpoints  K: checkpoint_path/seed{k}/ckpt_{score_epoch}.pth (K = 1: ckpt_E.pth)
   select_policy      global (reference) | stratified | balanced: per-class quotas (--policy)
   select_skip        ranks skipped from the top before the kept window (--skip)

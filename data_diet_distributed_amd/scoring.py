@@ -9,7 +9,11 @@ device-resident pipeline:
               over the pinned partition [b*B, (b+1)*B) (MIOpen) -> dd_el2n accumulates into the
               ensemble buffer (no per-example host syncs; reference :19-20 did 2 per example);
               the other logit scores (LOGIT_METHODS: loss, margin, entropy, error, wrong_mass,
-              variability) come from the same logits, one dd_logit_scores launch beside it
+              variability) come from the same logits, one dd_logit_scores launch beside it;
+              "proto" keeps that forward's pooled feature rows and, once the checkpoint's
+              chunks are done, takes their distance to the class means over all ranks
+              (dd_class_feature_sums -> one int64 all-reduce -> dd_class_centroids ->
+              dd_proto_scores)
       GraNd : eval-BN forward with a tape of Conv2d/Linear (input, output) -> dd_el2n emits the
               residual e = d(sum CE)/d(logits) -> autograd back to every conv output only
               (weights frozen: no weight-gradient GEMMs) -> dd_conv_pegrad_sqnorm per conv
@@ -44,7 +48,8 @@ STD = (0.2023, 0.1994, 0.2010)
 class ScoreConfig:
     # subset of {"el2n", "grand"} + LOGIT_METHODS (loss, margin, entropy, error, wrong_mass,
     # variability: the other scores of the EL2N forward, dd_logit_scores; the whole logit
-    # family shares one forward per checkpoint)
+    # family shares one forward per checkpoint) + FEATURE_METHODS ("proto": the distance of the
+    # pooled feature row to its class's mean over the whole dataset, from that same forward)
     methods: Sequence[str] = ("el2n",)
     select_by: str = "el2n"                  # which ensemble score ranks the keep-set
     batch_size: int = 128                    # EL2N batch partition (config.yaml:7 batch_size)
@@ -120,7 +125,7 @@ class ScoreConfig:
     def __post_init__(self):
         self.methods = tuple(self.methods)
         for m in self.methods:
-            if m not in ("el2n", "grand") + LOGIT_METHODS:
+            if m not in ("grand",) + FORWARD_FAMILY:
                 raise ValueError(f"unknown score method {m!r}")
         if self.select_by not in self.methods:
             raise ValueError(f"select_by={self.select_by!r} not among methods {self.methods}")
@@ -153,7 +158,7 @@ class ScoreConfig:
         if self.refine is True and not self.default_selection():
             raise ValueError("refine=True needs the default selection (select_policy='global', "
                              "select_skip=0): the refinement re-scores around one threshold")
-        if self.refine is True and self.select_by in LOGIT_METHODS:
+        if self.refine is True and self.select_by in LOGIT_METHODS + FEATURE_METHODS:
             raise ValueError(f"refine=True re-scores EL2N or GraNd only (select_by="
                              f"{self.select_by!r})")
         if self.el2n_chunk < self.batch_size:
@@ -171,11 +176,28 @@ SELECT_POLICIES = ("global", "stratified", "balanced")
 # standard deviation of wrong_mass over the checkpoints.  Larger means harder for every one.
 LOGIT_METHODS = _capi.LOGIT_STATS + ("variability",)
 LOGIT_FAMILY = ("el2n",) + LOGIT_METHODS  # the scores of one train-BN forward per checkpoint
+# Scores of that forward's pooled feature rows f_i (the rows the classifier consumes):
+#   proto_i = || f_i - mu_{y_i} ||_2,  mu_c = the mean of f_i over the WHOLE dataset's class c
+# (Sorscher et al.'s prototypicality; larger = more atypical).  Not a function of one row: the
+# class means are summed in exact fixed point over chunks, lanes and ranks (include/dd_capi.h
+# dd_class_feature_sums), which keeps the scores bitwise independent of all three.
+FEATURE_METHODS = ("proto",)
+# everything the EL2N forward produces: one forward per checkpoint and chunk serves them all
+FORWARD_FAMILY = LOGIT_FAMILY + FEATURE_METHODS
 
 
 def pass_of(method: str) -> str:
-    """The pass that computes `method`: "el2n" (the logit family's shared forward) or "grand"."""
-    return "el2n" if method in LOGIT_FAMILY else "grand"
+    """The pass that computes `method`: "el2n" (the shared forward of the logit family and the
+    feature scores) or "grand"."""
+    return "el2n" if method in FORWARD_FAMILY else "grand"
+
+
+def check_class_sizes(largest: int):
+    """The proto score's fixed-point class sums (|q| < 2^39 per element, int64) hold fewer than
+    2^24 members per class: reject a larger class."""
+    if largest >= _capi.PROTO_MAX_CLASS:
+        raise ValueError(f"proto: a class of {largest} members; the exact int64 feature sums "
+                         f"hold fewer than {_capi.PROTO_MAX_CLASS} (2^24) per class")
 
 
 def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
@@ -637,6 +659,7 @@ class ScoringEngine:
             return self._el2n_pass_grouped(model, images_u8, labels, lo, hi, accum)
         xbuf = torch.zeros((B,) + tuple(images_u8.shape[1:]), dtype=torch.float32,
                            device=self.device)
+        feats = self._feature_rows(accum)
         with torch.inference_mode():
             for b0 in range(lo, hi, B):
                 b1 = min(hi, b0 + B)
@@ -646,10 +669,24 @@ class ScoringEngine:
                 if pad:
                     xbuf[n:].zero_()
                     x = xbuf
-                logits = model.run(x, bn=self.cfg.el2n_bn, n_valid=n if pad else None,
-                                   fast=self.cfg.fast_convs)
+                if feats is None:
+                    logits = model.run(x, bn=self.cfg.el2n_bn, n_valid=n if pad else None,
+                                       fast=self.cfg.fast_convs)
+                else:
+                    # the same one forward; its tape ends with the classifier's input rows
+                    tape = []
+                    logits = model.run(x, bn=self.cfg.el2n_bn, n_valid=n if pad else None,
+                                       fast=self.cfg.fast_convs, tape=tape)
+                    feats[b0 - lo:b1 - lo].copy_(tape[-1][1][:n])
+                    del tape
                 logits = logits[:n].float().contiguous()
                 self._score_logits(model, logits, labels[b0:b1], accum, b0 - lo, b1 - lo)
+
+    @staticmethod
+    def _feature_rows(accum) -> Optional[torch.Tensor]:
+        """The shard's feature buffer [n, D] among the forward family's targets (score_shard
+        puts it there when a feature score is requested), else None."""
+        return accum.get("proto_features") if isinstance(accum, dict) else None
 
     def _el2n_pass_grouped(self, model: ResNet, images_u8, labels, lo, hi, accum):
         """el2n_pass on the hand-scheduled forward: `el2n_chunk` examples (whole pinned BN
@@ -670,6 +707,7 @@ class ScoringEngine:
         # leak into the other lanes' interleaved chunks)
         xbuf = torch.zeros((CH,) + tuple(images_u8.shape[1:]), dtype=torch.float32,
                            device=self.device)
+        feats = self._feature_rows(accum)
         for ci in range(lane, len(plan), lanes):
             b0, b1 = plan[ci]
             self._beat("el2n", ci, len(plan))
@@ -680,7 +718,13 @@ class ScoringEngine:
                 if n < nr:
                     xb[n:].zero_()
                 self._normalize(images_u8[b0:b1], xb[:n])
-                logits = el2n_fast.forward_logits(model, xb, B, n)[:n]
+                if feats is None:
+                    logits = el2n_fast.forward_logits(model, xb, B, n)[:n]
+                else:
+                    # only the valid rows reach the feature buffer (never a ragged chunk's padding)
+                    logits, f = el2n_fast.forward_features(model, xb, B, n)
+                    feats[b0 - lo:b1 - lo].copy_(f[:n])
+                    logits = logits[:n]
                 self._score_logits(model, logits, labels[b0:b1], accum, b0 - lo, b1 - lo)
             yield
 
@@ -768,19 +812,25 @@ class ScoringEngine:
     def _lanes_apply(self) -> bool:
         """Lanes interleave the chunk generators of the hand-scheduled passes."""
         c = self.cfg
-        el2n_ok = not any(m in LOGIT_FAMILY for m in c.methods) or (
+        el2n_ok = not any(m in FORWARD_FAMILY for m in c.methods) or (
             c.fast_el2n and c.fast_convs and c.el2n_bn == "batch"
             and all(el2n_fast.applicable(m) for m in self.models))
         return el2n_ok
 
     def score_shard(self, images_u8: torch.Tensor, labels: torch.Tensor, lo: int, hi: int,
-                    check: bool = True) -> Dict[str, torch.Tensor]:
+                    check: bool = True, group=None) -> Dict[str, torch.Tensor]:
         """Ensemble-mean scores of examples [lo, hi) (device tensors [hi-lo]).
 
         check=True (a direct, single-rank call) raises here: LabelError for labels outside
         [0, C) (reference :17), ValueError for non-finite scores (a forward that left fp16's
         range).  run() passes check=False and checks the gathered vectors instead (_validate),
-        so that on W > 1 ranks every rank raises (or falls back) together."""
+        so that on W > 1 ranks every rank raises (or falls back) together.
+
+        "proto" is the one score for which a shard is not a slice of the whole: its class
+        prototypes are means over every rank's rows.  run() passes its process `group`, and
+        the fixed-point class sums (and, once per call, the class counts) are all-reduced over
+        it, one collective per checkpoint, issued by every rank in the same order.  A direct
+        call without a group takes the prototypes over [lo, hi) only."""
         n = hi - lo
         K = len(self.models)
         self._bad = _capi.label_counter(self.device)
@@ -789,19 +839,42 @@ class ScoringEngine:
         self._bad_pass = (pass_of(self.cfg.methods[0]), self.models[0])
         accs = {m: torch.zeros(n, dtype=torch.float32, device=self.device)
                 for m in self.cfg.methods}
-        # the logit family (el2n + LOGIT_METHODS) shares one forward per checkpoint and chunk:
-        # its pass takes all the requested members' accumulators at once (_score_logits)
-        family = {m: accs[m] for m in self.cfg.methods if m in LOGIT_FAMILY}
+        # everything the EL2N forward produces (the logit family: el2n + LOGIT_METHODS, and the
+        # feature scores) shares one forward per checkpoint and chunk: its pass takes all the
+        # requested members' accumulators at once (_score_logits; proto_phase below)
+        family = {m: accs[m] for m in self.cfg.methods if m in FORWARD_FAMILY}
         if "variability" in family:  # accs["variability"] is Welford's M2, this is its mean
             family["variability_mean"] = torch.zeros_like(accs["variability"])
+        proto = self._proto_setup(labels[lo:hi], family, group) if "proto" in family else None
         kinds = list(dict.fromkeys(pass_of(m) for m in self.cfg.methods))  # first-use order
         targets = {"el2n": family, "grand": accs.get("grand")}
         buffers = {"el2n": list(family.values()), "grand": [accs.get("grand")]}
+
+        def proto_phase():
+            """The second phase of a checkpoint with proto requested, on the current stream,
+            after every chunk of the checkpoint has written its feature rows: one sums launch
+            over the shard, one all-reduce, the centroids, one distance launch."""
+            sums, bad_feat = proto["sums"], proto["bad_feat"]
+            C, D = sums.shape
+            proto["reduce"].zero_()
+            bad_feat.zero_()
+            _capi.class_feature_sums(proto["features"], proto["labels"], sums, bad_feat,
+                                     order=proto["order"])
+            if world_of(group) > 1:
+                # one int64 buffer: the sums, then the per-class counts of unrepresentable rows
+                proto["reduce"][C * D:].copy_(bad_feat)
+                _all_reduce_sum(proto["reduce"], group)
+                bad_feat.copy_(proto["reduce"][C * D:])
+            _capi.class_centroids(sums, proto["counts"], bad_feat, out=proto["centroids"])
+            _capi.proto_scores(proto["features"], proto["labels"], proto["centroids"],
+                               accum=accs["proto"])
 
         def passes(kind):
             for model in self.models:
                 if kind == "el2n":
                     self.el2n_pass(model, images_u8, labels, lo, hi, family)
+                    if proto is not None:
+                        proto_phase()
                 else:
                     self.grand_pass(model, images_u8, labels, lo, hi, accs["grand"])
 
@@ -824,6 +897,20 @@ class ScoringEngine:
                             with torch.cuda.stream(streams[j]):
                                 if next(its[j], StopIteration) is StopIteration:
                                     live.remove(j)
+                    if kind == "el2n" and proto is not None:
+                        # on lane 0's stream, after every lane's last chunk of this checkpoint;
+                        # the next checkpoint's chunks, which overwrite the feature buffer,
+                        # wait for the distance launch (stream waits, no host sync)
+                        for st in streams[1:]:
+                            streams[0].wait_stream(st)
+                        with torch.cuda.stream(streams[0]):
+                            proto_phase()
+                        for st in streams[1:]:
+                            st.wait_stream(streams[0])
+            if proto is not None:
+                for t in proto.values():
+                    for st in streams:
+                        t.record_stream(st)
             for st in streams:
                 for kind in kinds:
                     for acc in buffers[kind]:
@@ -837,7 +924,8 @@ class ScoringEngine:
             side.wait_stream(main)  # inputs and accumulators are ready on the main stream
             with torch.cuda.stream(side):
                 passes(kinds[0])
-            for acc in buffers[kinds[0]]:
+            for acc in buffers[kinds[0]] + (list(proto.values()) if proto is not None
+                                            and kinds[0] == "el2n" else []):
                 acc.record_stream(side)
             for kind in kinds[1:]:
                 passes(kind)
@@ -861,12 +949,51 @@ class ScoringEngine:
                     # e.g. an activation past fp16's range (65504) in a forward on fp16 operand
                     # halves: fail loudly rather than return non-finite scores (run() re-scores
                     # on bf16 halves by itself)
-                    ops = "el2n_operands" if m in LOGIT_FAMILY else "grand_operands"
+                    ops = "el2n_operands" if m in FORWARD_FAMILY else "grand_operands"
                     raise ValueError(f"non-finite {m} scores" + (
                         f": an activation of the forward may have left fp16's range; score "
                         f"with {ops}='bf16x3' (ScoreConfig), or through run(), which falls "
                         f"back to bf16 halves by itself" if self._f16_forward(m) else ""))
         return out
+
+    def _proto_setup(self, labels: torch.Tensor, family: dict, group) -> Dict[str, torch.Tensor]:
+        """The per-call state of the proto score for the shard's `labels` [n], allocated once and
+        reused by every checkpoint: the [n, D] fp32 feature buffer (n D 4 bytes: 102 MB at
+        50 000 x 512, 10.5 GB for 1.28 M x 2048 rows on one rank; also put among the forward's
+        targets, where the chunks find it), the rows' order sorted by label, the class counts
+        over every rank (dd_class_counts + one all-reduce: labels do not change across
+        checkpoints), and the int64 buffer [C D + C] that is all-reduced per checkpoint."""
+        n = labels.numel()
+        lin = self.models[0].linear
+        C, D = lin.out_features, lin.in_features
+        if D > _capi.PROTO_MAX_D:
+            raise ValueError(f"proto: feature width {D} above {_capi.PROTO_MAX_D}")
+        labels = labels.contiguous()
+        world = world_of(group)
+        counts, bad = _capi.class_counts(labels, C, check=False)
+        if world > 1:
+            _all_reduce_sum(counts, group)
+        if (self._bad_pass[0] == "el2n"
+                and not any(m in LOGIT_FAMILY for m in self.cfg.methods)):
+            self._bad.add_(bad)  # no logit kernel runs to count the labels outside [0, C)
+        # the fixed-point sums hold fewer than 2^24 members per class; the shards are balanced
+        # to within a batch, so the counts are read back only where the set could be that large
+        if world * (n + self.cfg.batch_size) >= _capi.PROTO_MAX_CLASS:
+            check_class_sizes(int(counts.max().item()))
+        dev = self.device
+        reduce = torch.zeros(C * D + C, dtype=torch.int64, device=dev)
+        state = {
+            "features": torch.empty((n, D), dtype=torch.float32, device=dev),
+            "labels": labels,
+            "order": torch.argsort(labels, stable=True),
+            "counts": counts,
+            "reduce": reduce,
+            "sums": reduce[:C * D].view(C, D),
+            "bad_feat": torch.zeros(C, dtype=torch.int32, device=dev),
+            "centroids": torch.empty((C, D), dtype=torch.float32, device=dev),
+        }
+        family["proto_features"] = state["features"]
+        return state
 
     def _counter(self, method: str, model) -> Optional[torch.Tensor]:
         """dd_el2n's label counter for the pass (method, model), or None (see score_shard)."""
@@ -888,9 +1015,12 @@ class ScoringEngine:
                                              shard and gathers again; the engine keeps the bf16
                                              packs (`fallback` records it; EL2N on bf16 halves
                                              then takes the near-threshold fp32 re-scoring,
-                                             refine "auto"); the logit family shares its
-                                             forward, so one non-finite member re-scores
-                                             every requested member;
+                                             refine "auto"); the forward family (the logit
+                                             scores and proto) shares its forward, so one
+                                             non-finite member re-scores every requested
+                                             member (a non-finite or out-of-range feature
+                                             row makes its class's proto scores NaN on
+                                             every rank: dd_class_centroids);
           anything else non-finite        -> ValueError (the selection would reject NaN)."""
         ms = list(full)
         if not ms or N == 0:
@@ -903,10 +1033,10 @@ class ScoringEngine:
             _all_reduce_sum(bad, group)
         _capi.check_labels(bad, self.models[0].linear.out_features, "run")
         redo = [m for i, m in enumerate(ms) if not bool(fin[i]) and self._f16_forward(m)]
-        if any(m in LOGIT_FAMILY for m in redo):
+        if any(m in FORWARD_FAMILY for m in redo):
             # the logit family shares its forward: the whole requested family is re-scored, in
             # one forward per checkpoint again
-            redo = [m for m in ms if m in LOGIT_FAMILY or m in redo]
+            redo = [m for m in ms if m in FORWARD_FAMILY or m in redo]
         if redo:
             ops = {"el2n": "el2n_operands", "grand": "grand_operands"}
             self.cfg = dataclasses.replace(self.cfg,
@@ -942,7 +1072,7 @@ class ScoringEngine:
         c = self.cfg
         if not c.fast_convs:
             return False
-        if method in LOGIT_FAMILY:  # one forward for the whole family
+        if method in FORWARD_FAMILY:  # one forward for the whole family
             return c.el2n_operands == "f16x3"
         return c.grand_operands == "f16x3" and c.fold_bn
 
@@ -963,13 +1093,13 @@ class ScoringEngine:
 
         def score(lo, hi):
             if n_total is None:
-                return self.score_shard(images_u8, labels, lo, hi, check=False)
+                return self.score_shard(images_u8, labels, lo, hi, check=False, group=group)
             if labels.numel() != hi - lo or images_u8.shape[0] != hi - lo:
                 raise ValueError(f"this rank's shard is [{lo}, {hi}) of {N}: got "
                                  f"{images_u8.shape[0]} images / {labels.numel()} labels")
             # shards are batch-aligned, so the partition anchored at 0 of the shard equals
             # the global one
-            return self.score_shard(images_u8, labels, 0, hi - lo, check=False)
+            return self.score_shard(images_u8, labels, 0, hi - lo, check=False, group=group)
 
         def select(keys, k):
             c = self.cfg
@@ -1002,7 +1132,8 @@ class ScoringEngine:
         c = self.cfg
         if c.refine is False or not c.default_selection():
             return False
-        if method in LOGIT_METHODS:  # the refinement re-scores EL2N and GraNd only
+        # the refinement re-scores EL2N and GraNd only
+        if method in LOGIT_METHODS + FEATURE_METHODS:
             return False
         if method == "el2n":
             if c.refine == "auto" and c.el2n_operands == "f16x3":

@@ -602,6 +602,58 @@ int dd_select_topk_by_class(const float* keys, const int64_t* labels, int64_t n,
                             int32_t* err_out, void* workspace, size_t workspace_bytes,
                             void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Distance to the class prototype in feature space (absent from the reference, whose one score
+ * is a function of the logits).  Purely additive: no existing signature or result changes, so
+ * dd_abi_version() stays 10.
+ *
+ *   mu_c    = mean of f_i over every example of the dataset with label c
+ *   proto_i = || f_i - mu_{y_i} ||_2          (f_i fp32 [D]: the row the classifier consumes)
+ *
+ * The mean spans launch chunks, lanes and ranks, so it is summed in fixed point: exact integer
+ * addition is order-free, which keeps the scores bitwise independent of the chunk size, the lane
+ * count and the world size (a float sum over shards could not).  Integer atomics only.
+ * Limits of all three: 1 <= D <= 4096 (dd_linear_forward's), 1 <= C <= 2^20, n (B) < 2^31;
+ * outside them, or a NULL buffer that the call would touch, is DD_EINVAL before any launch.
+ * No allocation, no synchronisation inside (graph-capturable).
+ *
+ * dd_class_feature_sums: feat fp32 [n][D], labels int64 [n], sums int64 [C][D], bad_feat int32
+ *   [C] (device).  sums[y_i][d] += q(f_i[d]) with q(v) = round-to-nearest-even(v * 2^24) as
+ *   int64.  It ACCUMULATES (the caller clears both buffers): two calls over a split of the rows
+ *   equal one call over all of them, whatever the split, the row order or the launch geometry.
+ *   A row with an element that is NaN, infinite or has |v| >= 2^15 adds nothing to sums and adds
+ *   one to bad_feat[y_i].  A row whose label lies outside [0, C) adds nothing anywhere (dd_el2n /
+ *   dd_logit_scores count such rows).  |q| < 2^39, so a class of fewer than 2^24 members cannot
+ *   overflow; the caller rejects larger classes (dd_class_counts gives the sizes).
+ *   order int64 [n] or NULL: the sequence in which the rows are visited, meant to be the rows
+ *   stable-sorted by label; an entry outside [0, n) names no row.  A workgroup takes a run of
+ *   consecutive entries and every column, sums in int64 registers while the class stays the same
+ *   and issues one 64-bit atomic per column when it changes and at the end of the run: about
+ *   (n / rows-per-workgroup + C) D atomics.  NULL takes the rows as they lie: the same sums,
+ *   more atomics.  n == 0 returns DD_OK.
+ *
+ * dd_class_centroids: counts int64 [C] (dd_class_counts), centroids fp32 [C][D]:
+ *   centroids[c][d] = (float)(((double)sums[c][d] / (double)counts[c]) * 2^-24);
+ *   0 where counts[c] == 0 (nothing reads it); NaN where bad_feat[c] != 0, so that every member
+ *   of a class with an unrepresentable row scores NaN, on every rank alike.
+ *
+ * dd_proto_scores: feat fp32 [B][D], labels int64 [B], centroids fp32 [C][D]; score / accum fp32
+ *   [B], either may be NULL but not both:
+ *   score[b] = sqrt(sum_d (feat[b][d] - centroids[y_b][d])^2) in fp32;  accum[b] += score[b].
+ *   A label outside [0, C) gives NaN (dd_el2n's rule), a NaN or infinite feature gives NaN.
+ *   Each row is reduced from that row alone in an order fixed by D alone: bitwise independent
+ *   of B, of the row's position and of the buffers' alignment.  B == 0 returns DD_OK.
+ * ---------------------------------------------------------------------------------------- */
+int dd_class_feature_sums(const float* feat, const int64_t* labels, const int64_t* order,
+                          int64_t n, int32_t D, int64_t C, int64_t* sums, int32_t* bad_feat,
+                          void* stream);
+
+int dd_class_centroids(const int64_t* sums, const int64_t* counts, const int32_t* bad_feat,
+                       int64_t C, int32_t D, float* centroids, void* stream);
+
+int dd_proto_scores(const float* feat, const int64_t* labels, const float* centroids, int64_t B,
+                    int32_t D, int64_t C, float* score, float* accum, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
