@@ -46,6 +46,7 @@ EXPORTS = (
     "dd_class_counts", "dd_select_by_class_workspace_bytes", "dd_select_topk_by_class",
     "dd_logit_scores", "dd_variability_finalize",
     "dd_class_feature_sums", "dd_class_centroids", "dd_proto_scores",
+    "dd_nn_workspace_bytes", "dd_nn_same_class",
 )
 
 
@@ -97,6 +98,9 @@ def lib():
                 "dd_class_feature_sums": (I32, [P, P, P, I64, I32, I64, P, P, P]),
                 "dd_class_centroids": (I32, [P, P, P, I64, I32, P, P]),
                 "dd_proto_scores": (I32, [P, P, P, I64, I32, I64, P, P, P]),
+                "dd_nn_workspace_bytes": (SZ, [I64, I64, I32, I32]),
+                "dd_nn_same_class": (I32, [P, P, P, I64, P, P, P, I64, I64, I32, I32, P, P, P,
+                                           P, SZ, P]),
                 "dd_conv_pegrad_method": (I32, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_workspace_bytes": (SZ, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_sqnorm": (I32, [P, P, ctypes.POINTER(ConvGeom), P, I32, I32, P,
@@ -450,6 +454,57 @@ def proto_scores(feat: torch.Tensor, labels: torch.Tensor, centroids: torch.Tens
     _check(rc, "dd_proto_scores")
     _t1(e0, "el2n", B * (4.0 * D + 8 + (4 if score is not None else 0) +
                          (8 if accum is not None else 0)), feat)
+
+
+# ---- distance to the nearest neighbour of the same class --------------------------------------
+def nn_workspace_bytes(nq: int, nc: int, D: int, operands: str = "f16x3") -> int:
+    """Bytes of nn_same_class's workspace (dd_nn_workspace_bytes; 0 for sizes outside the
+    entry point's limits)."""
+    return int(lib().dd_nn_workspace_bytes(int(nq), int(nc), int(D), OPERANDS[operands]))
+
+
+def nn_same_class(q: torch.Tensor, q_id: torch.Tensor, q_off: torch.Tensor, c: torch.Tensor,
+                  c_id: torch.Tensor, c_off: torch.Tensor, operands: str = "f16x3", dist=None,
+                  nn_id=None, accum=None, workspace=None):
+    """Per row of q [nq, D]: the nearest row of c [nc, D] within the same class segment
+    (q_off / c_off int64 [C + 1] on the device; both row sets grouped by class) whose c_id
+    differs from the row's q_id (dd_nn_same_class).  Writes whichever of dist fp32 [nq], nn_id
+    int64 [nq] and accum fp32 [nq] (+=) are given; +inf / -1 without a candidate, NaN / -1 for a
+    non-finite query row.  workspace: a uint8 tensor of nn_workspace_bytes, or None to allocate
+    one.  Returns the workspace."""
+    _dev(q, torch.float32, "q", 2)
+    _dev(c, torch.float32, "c", 2)
+    nq, D = q.shape
+    nc = c.shape[0]
+    if c.shape[1] != D:
+        raise ValueError(f"c must be [nc, {D}] (got {tuple(c.shape)})")
+    C = q_off.numel() - 1
+    if C < 1 or c_off.numel() != C + 1:
+        raise ValueError("q_off and c_off must both have C + 1 >= 2 entries")
+    if dist is None and nn_id is None and accum is None:
+        raise ValueError("nn_same_class: no output requested")
+    code = _operands_code(operands)
+    need = int(lib().dd_nn_workspace_bytes(nq, nc, D, code))
+    if need == 0:
+        raise ValueError(f"nn_same_class: unsupported size nq={nq}, nc={nc}, D={D}")
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ptrs = [_opt(dist, torch.float32, "dist", nq), _opt(nn_id, torch.int64, "nn_id", nq),
+            _opt(accum, torch.float32, "accum", nq)]
+    if nq == 0:  # nothing to do (and an empty tensor's pointer is NULL: "not requested")
+        return workspace
+    Dp = (D + 15) // 16 * 16
+    e0 = _t0(q, always=True)
+    rc = lib().dd_nn_same_class(
+        _dev(q, torch.float32, "q"), _opt(q_id, torch.int64, "q_id", nq),
+        _dev(q_off, torch.int64, "q_off", 1), nq, _opt(c if nc else None, torch.float32, "c"),
+        _opt(c_id if nc else None, torch.int64, "c_id", nc), _dev(c_off, torch.int64, "c_off", 1),
+        nc, C, D, code, *ptrs, _dev(workspace, torch.uint8, "workspace"),
+        workspace.numel() * workspace.element_size(), _stream(q))
+    _check(rc, "dd_nn_same_class")
+    # the fp32 rows read twice (pack, value), the halves written once
+    _t1(e0, "el2n", (nq + nc) * (8.0 * D + 4.0 * Dp), q)
+    return workspace
 
 
 def label_counter(device) -> torch.Tensor:

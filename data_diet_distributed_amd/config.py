@@ -16,7 +16,8 @@ REFERENCE_KEYS = ("device", "sparse", "sparsity", "batch_size_scores", "num_work
 DEFAULTS = {
     # el2n and/or grand and/or the other logit scores of the EL2N forward: loss | margin |
     # entropy | error | wrong_mass | variability (scoring.LOGIT_METHODS) | proto (the distance
-    # to the class prototype in feature space, scoring.FEATURE_METHODS); select_by takes any
+    # to the class prototype in feature space, scoring.FEATURE_METHODS) | nn (the distance to
+    # the nearest other example of the same class, scoring.NEIGHBOR_METHODS); select_by takes any
     "score_methods": ["el2n"],
     "select_by": "el2n",
     "select_policy": "global",        # global (reference) | stratified | balanced class quotas

@@ -56,7 +56,8 @@ def _score_rows(logits, labels, out, bad, score="el2n"):
 def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect=None,
                             score="el2n"):
     """Scores of every example the loader yields, in visit order, plus the visited indices
-    (`score`: "el2n" or one of _capi.LOGIT_STATS, from the same logits).
+    (`score`: "el2n" or one of _capi.LOGIT_STATS, from the same logits; or "nn", the distance to
+    the nearest visited example of the same class, from the rows `net.linear` consumes).
     A dict given as `collect` receives "labels" (the targets in visit order, int64 on the
     device) and "num_classes" (the width of the logits), for the class selection policies.
 
@@ -66,25 +67,41 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
     scores, visit, targets = [], [], []
     bad = _capi.label_counter(device)
     C = None
-    with torch.no_grad():
-        for _batch_idx, (idx, inp, target) in enumerate(train_loader):
-            inp = inp.to(device, non_blocking=True)
-            target = torch.as_tensor(target).to(device, non_blocking=True).to(torch.int64)
-            out = net(inp).float().contiguous()
-            if num_classes is not None and out.shape[1] != num_classes:
-                raise ValueError(f"net produces {out.shape[1]} classes, expected {num_classes}")
-            s = torch.empty(out.shape[0], dtype=torch.float32, device=out.device)
-            C = out.shape[1]
-            _score_rows(out, target.contiguous(), s, bad, score)
-            scores.append(s)
-            if collect is not None:
-                targets.append(target.flatten())
-            visit.append(torch.as_tensor(idx).to(out.device, non_blocking=True))
+    feats, hook = [], None
+    if score == "nn":  # the classifier's input rows of the same forward
+        head = getattr(net.module if hasattr(net, "module") else net, "linear", None)
+        if not isinstance(head, torch.nn.Linear):
+            raise ValueError("score='nn' needs a net whose classifier is `net.linear`")
+        hook = head.register_forward_pre_hook(
+            lambda _m, args: feats.append(args[0].detach().float().flatten(1)))
+    try:
+        with torch.no_grad():
+            for _batch_idx, (idx, inp, target) in enumerate(train_loader):
+                inp = inp.to(device, non_blocking=True)
+                target = torch.as_tensor(target).to(device, non_blocking=True).to(torch.int64)
+                out = net(inp).float().contiguous()
+                if num_classes is not None and out.shape[1] != num_classes:
+                    raise ValueError(f"net produces {out.shape[1]} classes, "
+                                     f"expected {num_classes}")
+                C = out.shape[1]
+                if hook is None:
+                    s = torch.empty(out.shape[0], dtype=torch.float32, device=out.device)
+                    _score_rows(out, target.contiguous(), s, bad, score)
+                    scores.append(s)
+                if collect is not None or hook is not None:
+                    targets.append(target.flatten())
+                visit.append(torch.as_tensor(idx).to(out.device, non_blocking=True))
+    finally:
+        if hook is not None:
+            hook.remove()
+    if hook is not None and visit:
+        from .scoring import nearest_same_class
+        scores = [nearest_same_class(torch.cat(feats).contiguous(), torch.cat(targets), C)]
     if collect is not None:
         collect["labels"] = (torch.cat(targets) if targets
                              else torch.empty(0, dtype=torch.int64, device=device))
         collect["num_classes"] = C
-    if not scores:
+    if not visit:
         return (torch.empty(0, dtype=torch.float32, device=device),
                 torch.empty(0, dtype=torch.int64, device=device))
     _capi.check_labels(bad, C, "sparse_loader")
@@ -307,6 +324,8 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
                     device=dev)
     scores = torch.empty(n, dtype=torch.float32, device=dev)
     bad = _capi.label_counter(dev)
+    feats = (torch.empty((n, model.linear.in_features), dtype=torch.float32, device=dev)
+             if score == "nn" else None)
     with torch.inference_mode():
         for c0 in range(0, n, CH):
             c1 = min(n, c0 + CH)
@@ -316,8 +335,14 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
                 xb[rows:].zero_()
             idx = visit_d[c0:c1]
             _capi.normalize_u8(img_d, mean, std, xb[:rows], index=idx)
+            if feats is not None:  # the same forward: its pooled feature rows
+                feats[c0:c1].copy_(el2n_fast.forward_features(model, xb, B, rows)[1][:rows])
+                continue
             logits = el2n_fast.forward_logits(model, xb, B, rows)[:rows]
             _score_rows(logits.contiguous(), lab_d[idx], scores[c0:c1], bad, score)
+        if feats is not None:  # neighbours among the visited examples (LabelError inside)
+            from .scoring import nearest_same_class
+            return nearest_same_class(feats, lab_d[visit_d], model.linear.out_features), visit_d
     # a label outside [0, C): the reference's one_hot raises (:17), so does this path
     _capi.check_labels(bad, model.linear.out_features, "sparse_loader")
     return scores, visit_d
@@ -390,6 +415,9 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     score: what ranks the examples: "el2n" (the reference's score), or one of the other
     single-forward logit scores "loss", "margin", "entropy", "error", "wrong_mass"
     (dd_logit_scores on the same logits; larger = harder, so policy / skip apply unchanged).
+    "nn" ranks by the distance to the nearest visited example of the same class in feature space
+    (the rows the classifier consumes, from the same single forward; dd_nn_same_class), so the
+    default policy drops near-duplicates first; a class with exactly one visited member raises.
     "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
     over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
     score="el2n"."""
@@ -398,8 +426,9 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     if score in ("variability", "grand", "proto"):
         raise ValueError(f"score={score!r} is computed by the scoring engine "
                          f"(scoring.ScoringEngine / score.py), not by sparse_loader")
-    if score != "el2n" and score not in _capi.LOGIT_STATS:
-        raise ValueError(f"score must be 'el2n' or one of {_capi.LOGIT_STATS} (got {score!r})")
+    if score not in ("el2n", "nn") and score not in _capi.LOGIT_STATS:
+        raise ValueError(f"score must be 'el2n', 'nn' or one of {_capi.LOGIT_STATS} "
+                         f"(got {score!r})")
     if refine is True and score != "el2n":
         raise ValueError("refine=True re-scores EL2N only: it needs score='el2n'")
     if policy not in SELECT_POLICIES:

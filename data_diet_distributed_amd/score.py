@@ -14,6 +14,8 @@ rest (config.DEFAULTS):
                      checkpoint for all of them): loss | margin | entropy | error |
                      wrong_mass | variability (needs K >= 2 to rank by), and proto (the
                      distance of the pooled feature row to its class mean, same forward)
+                     and nn (its distance to the nearest other row of the same class: a
+                     near-duplicate scores close to 0 and is dropped first)
   score_checkpoints  K: checkpoint_path/seed{k}/ckpt_{score_epoch}.pth (K = 1: ckpt_E.pth)
   select_policy      global (reference) | stratified | balanced: per-class quotas (--policy)
   select_skip        ranks skipped from the top before the kept window (--skip)

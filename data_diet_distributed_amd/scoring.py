@@ -13,7 +13,9 @@ device-resident pipeline:
               "proto" keeps that forward's pooled feature rows and, once the checkpoint's
               chunks are done, takes their distance to the class means over all ranks
               (dd_class_feature_sums -> one int64 all-reduce -> dd_class_centroids ->
-              dd_proto_scores)
+              dd_proto_scores); "nn" takes, from those same rows, the distance to the nearest
+              other row of the same class over all ranks (one all-gather of the rows ->
+              dd_nn_same_class: an all-pairs search per class on split MFMA)
       GraNd : eval-BN forward with a tape of Conv2d/Linear (input, output) -> dd_el2n emits the
               residual e = d(sum CE)/d(logits) -> autograd back to every conv output only
               (weights frozen: no weight-gradient GEMMs) -> dd_conv_pegrad_sqnorm per conv
@@ -50,6 +52,7 @@ class ScoreConfig:
     # variability: the other scores of the EL2N forward, dd_logit_scores; the whole logit
     # family shares one forward per checkpoint) + FEATURE_METHODS ("proto": the distance of the
     # pooled feature row to its class's mean over the whole dataset, from that same forward)
+    # + NEIGHBOR_METHODS ("nn": the distance to the nearest other row of the same class)
     methods: Sequence[str] = ("el2n",)
     select_by: str = "el2n"                  # which ensemble score ranks the keep-set
     batch_size: int = 128                    # EL2N batch partition (config.yaml:7 batch_size)
@@ -125,7 +128,7 @@ class ScoreConfig:
     def __post_init__(self):
         self.methods = tuple(self.methods)
         for m in self.methods:
-            if m not in ("grand",) + FORWARD_FAMILY:
+            if m not in ("grand",) + FORWARD_SCORES:
                 raise ValueError(f"unknown score method {m!r}")
         if self.select_by not in self.methods:
             raise ValueError(f"select_by={self.select_by!r} not among methods {self.methods}")
@@ -158,7 +161,8 @@ class ScoreConfig:
         if self.refine is True and not self.default_selection():
             raise ValueError("refine=True needs the default selection (select_policy='global', "
                              "select_skip=0): the refinement re-scores around one threshold")
-        if self.refine is True and self.select_by in LOGIT_METHODS + FEATURE_METHODS:
+        if self.refine is True and self.select_by in (LOGIT_METHODS + FEATURE_METHODS
+                                                      + NEIGHBOR_METHODS):
             raise ValueError(f"refine=True re-scores EL2N or GraNd only (select_by="
                              f"{self.select_by!r})")
         if self.el2n_chunk < self.batch_size:
@@ -184,12 +188,19 @@ LOGIT_FAMILY = ("el2n",) + LOGIT_METHODS  # the scores of one train-BN forward p
 FEATURE_METHODS = ("proto",)
 # everything the EL2N forward produces: one forward per checkpoint and chunk serves them all
 FORWARD_FAMILY = LOGIT_FAMILY + FEATURE_METHODS
+# Scores of a row against the other rows of its class, from the same feature rows:
+#   nn_i = min over j != i with y_j == y_i, over the WHOLE dataset, of || f_i - f_j ||_2
+# (the redundancy signal of SemDeDup and the density / coreset family: a near-duplicate scores
+# close to 0, so the default policy, which keeps the largest scores, drops duplicates first).
+NEIGHBOR_METHODS = ("nn",)
+# every score that comes from the EL2N forward
+FORWARD_SCORES = FORWARD_FAMILY + NEIGHBOR_METHODS
 
 
 def pass_of(method: str) -> str:
     """The pass that computes `method`: "el2n" (the shared forward of the logit family and the
     feature scores) or "grand"."""
-    return "el2n" if method in FORWARD_FAMILY else "grand"
+    return "el2n" if method in FORWARD_SCORES else "grand"
 
 
 def check_class_sizes(largest: int):
@@ -198,6 +209,69 @@ def check_class_sizes(largest: int):
     if largest >= _capi.PROTO_MAX_CLASS:
         raise ValueError(f"proto: a class of {largest} members; the exact int64 feature sums "
                          f"hold fewer than {_capi.PROTO_MAX_CLASS} (2^24) per class")
+
+
+def check_no_singleton_class(counts):
+    """The nn score of a class's only member would be infinite (no other row of its class):
+    reject a dataset with such a class, naming it.  counts: members per class over the whole
+    dataset (an empty class is fine)."""
+    for c, m in enumerate(counts):
+        if int(m) == 1:
+            raise ValueError(f"nn: class {c} has exactly one member in the whole dataset; its "
+                             f"nearest same-class neighbour does not exist (score +inf)")
+
+
+def shard_lengths(n: int, group=None):
+    """(rows per rank in rank order, this rank): one small all-gather, once per scoring call."""
+    world, rank = _world(group)
+    if world == 1:
+        return [int(n)], 0
+    dev = "cpu" if dist.get_backend(group) == "gloo" else torch.device("cuda",
+                                                                       torch.cuda.current_device())
+    parts = _all_gather_same(torch.tensor([int(n)], dtype=torch.int64, device=dev), group)
+    return [int(p.item()) for p in parts], rank
+
+
+def gather_rows(t: torch.Tensor, lengths, group=None) -> torch.Tensor:
+    """Every rank's rows [n_r, ...] in rank order -> [sum n_r, ...], one all-gather: the shards
+    are padded to the longest, as in gather_scores (gloo: staged through host memory).  With one
+    rank, `t` itself."""
+    if len(lengths) == 1:
+        return t
+    L = max(lengths)
+    buf = torch.zeros((L,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
+    buf[:t.shape[0]] = t
+    parts = _all_gather_same(buf, group)
+    return torch.cat([p[:m] for p, m in zip(parts, lengths)])
+
+
+def class_grouping(labels: torch.Tensor, num_classes: int):
+    """(order, offsets, counts, bad) of int64 device labels [n]: the rows stable-sorted by class
+    with the labels outside [0, C) last (past offsets[C]: in no class), the int64 [C + 1] class
+    offsets, and dd_class_counts' outputs."""
+    C = int(num_classes)
+    counts, bad = _capi.class_counts(labels, C, check=False)
+    key = torch.where((labels >= 0) & (labels < C), labels, torch.full_like(labels, C))
+    off = torch.zeros(C + 1, dtype=torch.int64, device=labels.device)
+    off[1:] = torch.cumsum(counts, 0)
+    return torch.argsort(key, stable=True), off, counts, bad
+
+
+def nearest_same_class(features: torch.Tensor, labels: torch.Tensor, num_classes: int,
+                       operands: str = "f16x3") -> torch.Tensor:
+    """fp32 [n]: each row's distance to the nearest other row of its class among `features`
+    [n, D] (one dd_nn_same_class launch; a tie goes to the smaller row index).  Raises
+    LabelError for a label outside [0, C) and ValueError for a class of exactly one member."""
+    labels = labels.contiguous()
+    order, off, counts, bad = class_grouping(labels, num_classes)
+    host = torch.cat([counts, bad.to(torch.int64)]).tolist()  # the one read of the counts
+    if host[-1]:
+        raise _capi.LabelError(f"nn: {host[-1]} label(s) outside [0, {int(num_classes)})")
+    check_no_singleton_class(host[:-1])
+    rows = features.index_select(0, order)
+    dist_sorted = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)
+    _capi.nn_same_class(rows, order, off, rows, order, off, operands=operands, dist=dist_sorted)
+    return torch.empty_like(dist_sorted).index_copy_(0, order, dist_sorted)
 
 
 def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
@@ -812,7 +886,7 @@ class ScoringEngine:
     def _lanes_apply(self) -> bool:
         """Lanes interleave the chunk generators of the hand-scheduled passes."""
         c = self.cfg
-        el2n_ok = not any(m in FORWARD_FAMILY for m in c.methods) or (
+        el2n_ok = not any(m in FORWARD_SCORES for m in c.methods) or (
             c.fast_el2n and c.fast_convs and c.el2n_bn == "batch"
             and all(el2n_fast.applicable(m) for m in self.models))
         return el2n_ok
@@ -830,7 +904,12 @@ class ScoringEngine:
         prototypes are means over every rank's rows.  run() passes its process `group`, and
         the fixed-point class sums (and, once per call, the class counts) are all-reduced over
         it, one collective per checkpoint, issued by every rank in the same order.  A direct
-        call without a group takes the prototypes over [lo, hi) only."""
+        call without a group takes the prototypes over [lo, hi) only.
+
+        "nn" is the other one: a row's nearest neighbour may lie on another rank.  With the
+        `group`, the shard labels are all-gathered once per call and the feature rows once per
+        checkpoint (every rank in the same order), and each rank searches its own rows among
+        the whole dataset's.  A direct call without a group searches [lo, hi) only."""
         n = hi - lo
         K = len(self.models)
         self._bad = _capi.label_counter(self.device)
@@ -842,10 +921,14 @@ class ScoringEngine:
         # everything the EL2N forward produces (the logit family: el2n + LOGIT_METHODS, and the
         # feature scores) shares one forward per checkpoint and chunk: its pass takes all the
         # requested members' accumulators at once (_score_logits; proto_phase below)
-        family = {m: accs[m] for m in self.cfg.methods if m in FORWARD_FAMILY}
+        family = {m: accs[m] for m in self.cfg.methods if m in FORWARD_SCORES}
         if "variability" in family:  # accs["variability"] is Welford's M2, this is its mean
             family["variability_mean"] = torch.zeros_like(accs["variability"])
         proto = self._proto_setup(labels[lo:hi], family, group) if "proto" in family else None
+        nn = self._nn_setup(labels[lo:hi], family, group) if "nn" in family else None
+        # the buffers of the second phase, for the streams' bookkeeping below
+        phase_state = (list(proto.values()) if proto is not None else []) + [
+            t for t in (nn.values() if nn is not None else ()) if isinstance(t, torch.Tensor)]
         kinds = list(dict.fromkeys(pass_of(m) for m in self.cfg.methods))  # first-use order
         targets = {"el2n": family, "grand": accs.get("grand")}
         buffers = {"el2n": list(family.values()), "grand": [accs.get("grand")]}
@@ -869,12 +952,33 @@ class ScoringEngine:
             _capi.proto_scores(proto["features"], proto["labels"], proto["centroids"],
                                accum=accs["proto"])
 
+        def nn_phase():
+            """The same point of a checkpoint with nn requested: one all-gather of the feature
+            rows (world > 1), the rows gathered into class order, one dd_nn_same_class launch
+            that accumulates in class order (scattered back to shard order after the last
+            checkpoint)."""
+            feats = nn["features"]
+            torch.index_select(feats, 0, nn["q_order"], out=nn["q"])
+            allf = gather_rows(feats, nn["lengths"], group)
+            if allf is feats:
+                cand = nn["q"]  # one rank: the candidates are the queries
+            else:
+                cand = torch.index_select(allf, 0, nn["c_order"], out=nn["c"])
+            nn["workspace"] = _capi.nn_same_class(
+                nn["q"], nn["q_id"], nn["q_off"], cand, nn["c_id"], nn["c_off"],
+                operands=self.cfg.el2n_operands, accum=nn["accum"], workspace=nn["workspace"])
+
+        def second_phase():
+            if proto is not None:
+                proto_phase()
+            if nn is not None:
+                nn_phase()
+
         def passes(kind):
             for model in self.models:
                 if kind == "el2n":
                     self.el2n_pass(model, images_u8, labels, lo, hi, family)
-                    if proto is not None:
-                        proto_phase()
+                    second_phase()
                 else:
                     self.grand_pass(model, images_u8, labels, lo, hi, accs["grand"])
 
@@ -897,20 +1001,19 @@ class ScoringEngine:
                             with torch.cuda.stream(streams[j]):
                                 if next(its[j], StopIteration) is StopIteration:
                                     live.remove(j)
-                    if kind == "el2n" and proto is not None:
+                    if kind == "el2n" and phase_state:
                         # on lane 0's stream, after every lane's last chunk of this checkpoint;
                         # the next checkpoint's chunks, which overwrite the feature buffer,
                         # wait for the distance launch (stream waits, no host sync)
                         for st in streams[1:]:
                             streams[0].wait_stream(st)
                         with torch.cuda.stream(streams[0]):
-                            proto_phase()
+                            second_phase()
                         for st in streams[1:]:
                             st.wait_stream(streams[0])
-            if proto is not None:
-                for t in proto.values():
-                    for st in streams:
-                        t.record_stream(st)
+            for t in phase_state:
+                for st in streams:
+                    t.record_stream(st)
             for st in streams:
                 for kind in kinds:
                     for acc in buffers[kind]:
@@ -924,8 +1027,7 @@ class ScoringEngine:
             side.wait_stream(main)  # inputs and accumulators are ready on the main stream
             with torch.cuda.stream(side):
                 passes(kinds[0])
-            for acc in buffers[kinds[0]] + (list(proto.values()) if proto is not None
-                                            and kinds[0] == "el2n" else []):
+            for acc in buffers[kinds[0]] + (phase_state if kinds[0] == "el2n" else []):
                 acc.record_stream(side)
             for kind in kinds[1:]:
                 passes(kind)
@@ -933,6 +1035,8 @@ class ScoringEngine:
         else:
             for kind in kinds:
                 passes(kind)
+        if nn is not None:  # class order -> shard order
+            accs["nn"].index_copy_(0, nn["q_order"], nn["accum"])
         out = {}
         for method in self.cfg.methods:
             res = torch.empty_like(accs[method])
@@ -949,7 +1053,7 @@ class ScoringEngine:
                     # e.g. an activation past fp16's range (65504) in a forward on fp16 operand
                     # halves: fail loudly rather than return non-finite scores (run() re-scores
                     # on bf16 halves by itself)
-                    ops = "el2n_operands" if m in FORWARD_FAMILY else "grand_operands"
+                    ops = "el2n_operands" if m in FORWARD_SCORES else "grand_operands"
                     raise ValueError(f"non-finite {m} scores" + (
                         f": an activation of the forward may have left fp16's range; score "
                         f"with {ops}='bf16x3' (ScoreConfig), or through run(), which falls "
@@ -995,6 +1099,52 @@ class ScoringEngine:
         family["proto_features"] = state["features"]
         return state
 
+    def _nn_setup(self, labels: torch.Tensor, family: dict, group) -> dict:
+        """The per-call state of the nn score for the shard's `labels` [n], built once and reused
+        by every checkpoint (labels do not change across checkpoints): the [n, D] feature buffer
+        (proto's when both are requested), every rank's labels (one all-gather), the class
+        offsets of the whole dataset and of this shard (dd_class_counts), the class-sorted order
+        of the candidates (all rows) and of the queries (this rank's rows) with their global ids,
+        the class-ordered row buffers, the class-ordered accumulator and the kernel's workspace
+        (4 (n + N) pad16(D) bytes).  The whole dataset's counts are read to the host once: a
+        class of exactly one member is rejected by name."""
+        n = labels.numel()
+        lin = self.models[0].linear
+        C, D = lin.out_features, lin.in_features
+        if D > _capi.PROTO_MAX_D:
+            raise ValueError(f"nn: feature width {D} above {_capi.PROTO_MAX_D}")
+        dev = self.device
+        labels = labels.contiguous()
+        lengths, rank = shard_lengths(n, group)
+        all_labels = gather_rows(labels, lengths, group)
+        base = sum(lengths[:rank])
+
+        q_order, q_off, counts, bad = class_grouping(labels, C)
+        if all_labels is labels:
+            c_order, c_off = q_order, q_off
+        else:
+            c_order, c_off, counts, _ = class_grouping(all_labels.contiguous(), C)
+        if (self._bad_pass[0] == "el2n"
+                and not any(m in FORWARD_FAMILY for m in self.cfg.methods)):
+            self._bad.add_(bad)  # neither a logit kernel nor proto counts the bad labels
+        check_no_singleton_class(counts.tolist())  # the one read of the counts
+        N = all_labels.numel()
+        feats = family.get("proto_features")
+        if feats is None:
+            feats = torch.empty((n, D), dtype=torch.float32, device=dev)
+            family["proto_features"] = feats  # where the chunks find the feature buffer
+        need = _capi.nn_workspace_bytes(n, N, D, self.cfg.el2n_operands)
+        return {
+            "features": feats, "lengths": lengths,
+            "q_order": q_order, "q_off": q_off, "q_id": q_order + base,
+            "c_order": c_order, "c_off": c_off, "c_id": c_order,
+            "q": torch.empty((n, D), dtype=torch.float32, device=dev),
+            "c": (torch.empty((N, D), dtype=torch.float32, device=dev)
+                  if all_labels is not labels else None),
+            "accum": torch.zeros(n, dtype=torch.float32, device=dev),
+            "workspace": torch.empty(max(need, 1), dtype=torch.uint8, device=dev),
+        }
+
     def _counter(self, method: str, model) -> Optional[torch.Tensor]:
         """dd_el2n's label counter for the pass (method, model), or None (see score_shard)."""
         bp = getattr(self, "_bad_pass", None)
@@ -1033,10 +1183,10 @@ class ScoringEngine:
             _all_reduce_sum(bad, group)
         _capi.check_labels(bad, self.models[0].linear.out_features, "run")
         redo = [m for i, m in enumerate(ms) if not bool(fin[i]) and self._f16_forward(m)]
-        if any(m in FORWARD_FAMILY for m in redo):
+        if any(m in FORWARD_SCORES for m in redo):
             # the logit family shares its forward: the whole requested family is re-scored, in
             # one forward per checkpoint again
-            redo = [m for m in ms if m in FORWARD_FAMILY or m in redo]
+            redo = [m for m in ms if m in FORWARD_SCORES or m in redo]
         if redo:
             ops = {"el2n": "el2n_operands", "grand": "grand_operands"}
             self.cfg = dataclasses.replace(self.cfg,
@@ -1072,7 +1222,7 @@ class ScoringEngine:
         c = self.cfg
         if not c.fast_convs:
             return False
-        if method in FORWARD_FAMILY:  # one forward for the whole family
+        if method in FORWARD_SCORES:  # one forward for the whole family
             return c.el2n_operands == "f16x3"
         return c.grand_operands == "f16x3" and c.fold_bn
 
@@ -1133,7 +1283,7 @@ class ScoringEngine:
         if c.refine is False or not c.default_selection():
             return False
         # the refinement re-scores EL2N and GraNd only
-        if method in LOGIT_METHODS + FEATURE_METHODS:
+        if method in LOGIT_METHODS + FEATURE_METHODS + NEIGHBOR_METHODS:
             return False
         if method == "el2n":
             if c.refine == "auto" and c.el2n_operands == "f16x3":

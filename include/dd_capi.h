@@ -654,6 +654,51 @@ int dd_class_centroids(const int64_t* sums, const int64_t* counts, const int32_t
 int dd_proto_scores(const float* feat, const int64_t* labels, const float* centroids, int64_t B,
                     int32_t D, int64_t C, float* score, float* accum, void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Distance to the nearest neighbour of the same class in feature space: a redundancy signal (a
+ * near-duplicate scores close to 0).  Purely additive: dd_abi_version() stays 10.
+ *
+ *   nn_r = min over candidates j of the query's class with c_id[j] != q_id[r] of || q_r - c_j ||_2
+ *
+ * q fp32 [nq][D] (queries) and c fp32 [nc][D] (candidates), both grouped by class: q_off / c_off
+ * int64 [C + 1] (device) give segment k of q, which is searched in segment k of c only; a segment
+ * may be empty.  Offsets that decrease or leave the buffers are clamped on the device (never an
+ * access outside); a query row outside every segment has no candidate.  q_id / c_id int64: the
+ * rows' global example indices; the candidate with the query's own id is skipped.
+ *
+ * The search minimises key(r, j) = ||c_j||^2 - 2 q_r . c_j over the segment, the dot product on
+ * split MFMA (hi.hi + hi.lo + lo.hi of the `operands` halves, fp32 accumulation, 32x32x16, D
+ * zero-padded to a multiple of 16, K order fixed by D), ||c_j||^2 in fp32 in an order fixed by
+ * D, and keeps the smallest (key, c_id) pair, compared lexicographically: a tie goes to the
+ * smaller id.  No atomics.  A candidate row with a non-finite element is never chosen (its key is
+ * NaN, and a NaN key is never the smaller one; so is the key of a pair whose halves leave the
+ * operand type's range, |v| >= 65504 in fp16).  The value is then taken in fp32 from the fp32
+ * rows, one row per wave in an order fixed by D (dd_proto_scores' reduction):
+ *   dist[r] = sqrt(sum_d (q[r][d] - c[pick][d])^2),  nn_id[r] = c_id[pick],  accum[r] += dist[r]
+ * so an exact duplicate scores exactly 0, and the MFMA rounding decides only WHICH neighbour is
+ * picked: d^2(pick) - d^2(best) <= 2 eps (||q||^2 + max_j ||c_j||^2) with
+ * eps = (2^-22 fp16 halves | 2^-16 bf16 halves) + (D + 2) 2^-24.
+ * No admissible candidate (a class of one): dist = +inf, nn_id = -1.  A query row with a
+ * non-finite element: dist = NaN, nn_id = -1.  Any of dist / nn_id / accum may be NULL, not all.
+ *
+ * dist[r] and nn_id[r] depend on row r, on the candidate SET of its class and on D: bitwise
+ * independent of the batching of the queries, of nq, of the rows' positions and the buffers'
+ * alignment, and of the launch geometry.
+ *
+ * Limits: 1 <= D <= 4096, 1 <= C <= 2^20, 0 <= nq, nc < 2^31, operands DD_OPERANDS_F16X3 or
+ * DD_OPERANDS_BF16X3; outside them, a NULL buffer the call would touch, or a workspace that is
+ * too small or not 16-byte aligned is DD_EINVAL with a message before any launch.  nq == 0
+ * returns DD_OK.  The workspace (dd_nn_workspace_bytes: host only, 0 for bad arguments) holds
+ * the halves of every row, split once per call: 4 (nq + nc) pad16(D) bytes, plus 4 (nq + nc).
+ * No allocation, no synchronisation inside (graph-capturable); plain vector stores only.
+ * ---------------------------------------------------------------------------------------- */
+size_t dd_nn_workspace_bytes(int64_t nq, int64_t nc, int32_t D, int32_t operands);
+
+int dd_nn_same_class(const float* q, const int64_t* q_id, const int64_t* q_off, int64_t nq,
+                     const float* c, const int64_t* c_id, const int64_t* c_off, int64_t nc,
+                     int64_t C, int32_t D, int32_t operands, float* dist, int64_t* nn_id,
+                     float* accum, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
