@@ -326,3 +326,22 @@ def forward_logits_fp32(model: ResNet, x: torch.Tensor, group_size: int,
     lin = model.linear
     return _capi.linear_forward(out.reshape(out.size(0), -1).contiguous(), lin.weight.detach(),
                                 None if lin.bias is None else lin.bias.detach())
+
+
+def fp32_group_launches(rows, step: int, B: int, shape, device, fill):
+    """The inputs of forward_logits_fp32 for the row ranges `rows` (whole BN groups of up to B
+    rows; only the last can be ragged, and it comes last), `step` groups per launch (the count
+    padded to a power of two, so MIOpen sees few distinct batch sizes).  `fill(dst, r0, r1)`
+    writes the normalised images of rows [r0, r1) into `dst` and returns their labels.  Yields
+    per launch (x zeroed [G * B, ...], sel = the positions of the rows in x, n_valid, the rows'
+    labels [sel.numel()])."""
+    for c in range(0, len(rows), step):
+        part = rows[c:c + step]
+        G = 1 << (len(part) - 1).bit_length()
+        x = torch.zeros((G * B,) + tuple(shape), dtype=torch.float32, device=device)
+        sel, labels = [], []
+        for gi, (r0, r1) in enumerate(part):
+            labels.append(fill(x[gi * B:gi * B + (r1 - r0)], r0, r1))
+            sel.append(torch.arange(gi * B, gi * B + (r1 - r0), device=device))
+        n_valid = (len(part) - 1) * B + (part[-1][1] - part[-1][0])
+        yield x, torch.cat(sel), n_valid, torch.cat(labels).contiguous()

@@ -95,7 +95,7 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
         if hook is not None:
             hook.remove()
     if hook is not None and visit:
-        from .scoring import nearest_same_class
+        from .forward_scores import nearest_same_class
         scores = [nearest_same_class(torch.cat(feats).contiguous(), torch.cat(targets), C)]
     if collect is not None:
         collect["labels"] = (torch.cat(targets) if targets
@@ -341,7 +341,7 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
             logits = el2n_fast.forward_logits(model, xb, B, rows)[:rows]
             _score_rows(logits.contiguous(), lab_d[idx], scores[c0:c1], bad, score)
         if feats is not None:  # neighbours among the visited examples (LabelError inside)
-            from .scoring import nearest_same_class
+            from .forward_scores import nearest_same_class
             return nearest_same_class(feats, lab_d[visit_d], model.linear.out_features), visit_d
     # a label outside [0, C): the reference's one_hot raises (:17), so does this path
     _capi.check_labels(bad, model.linear.out_features, "sparse_loader")
@@ -372,24 +372,17 @@ def refine_fast_keep_set(train_loader, src, model, device, scores, visit, sample
         last visit batch can be ragged, and it comes last), `refine_groups` batches per
         launch, each its own BN group."""
         outs = []
-        step = cfg.refine_groups
+
+        def fill(dst, r0, r1):
+            _capi.normalize_u8(img_d, mean, std, dst, index=visit[r0:r1])
+            return lab_d[visit[r0:r1]]
+
         with torch.inference_mode():
-            for c in range(0, len(rows), step):
-                part = rows[c:c + step]
-                G = 1 << (len(part) - 1).bit_length()  # few distinct MIOpen batch sizes
-                x = torch.zeros((G * B,) + tuple(img_d.shape[1:]), dtype=torch.float32,
-                                device=dev)
-                sel, idx = [], []
-                for gi, (r0, r1) in enumerate(part):
-                    ix = visit[r0:r1]
-                    _capi.normalize_u8(img_d, mean, std, x[gi * B:gi * B + (r1 - r0)], index=ix)
-                    sel.append(torch.arange(gi * B, gi * B + (r1 - r0), device=dev))
-                    idx.append(ix)
-                sel, idx = torch.cat(sel), torch.cat(idx)
-                n_valid = (len(part) - 1) * B + (part[-1][1] - part[-1][0])
+            for x, sel, n_valid, lab in el2n_fast.fp32_group_launches(
+                    rows, cfg.refine_groups, B, img_d.shape[1:], dev, fill):
                 logits = el2n_fast.forward_logits_fp32(model, x, B, n_valid)
                 out = torch.empty(sel.numel(), dtype=torch.float32, device=dev)
-                _capi.el2n(logits[sel].float().contiguous(), lab_d[idx].contiguous(), score=out)
+                _capi.el2n(logits[sel].float().contiguous(), lab, score=out)
                 outs.append(out)
         return torch.cat(outs)
 
@@ -421,7 +414,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
     over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
     score="el2n"."""
-    from .scoring import SELECT_POLICIES, normalize_refine, select_with_policy
+    from .methods import check_selection
+    from .scoring import normalize_refine, select_with_policy
     refine = normalize_refine(refine)
     if score in ("variability", "grand", "proto"):
         raise ValueError(f"score={score!r} is computed by the scoring engine "
@@ -431,10 +425,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                          f"(got {score!r})")
     if refine is True and score != "el2n":
         raise ValueError("refine=True re-scores EL2N only: it needs score='el2n'")
-    if policy not in SELECT_POLICIES:
-        raise ValueError(f"policy must be one of {SELECT_POLICIES} (got {policy!r})")
-    if isinstance(skip, bool) or not isinstance(skip, (int, np.integer)) or skip < 0:
-        raise ValueError(f"skip must be an integer >= 0 (got {skip!r})")
+    skip = check_selection(policy, skip, "policy", "skip")
     default_rule = policy == "global" and skip == 0
     if refine is True and not default_rule:
         raise ValueError("refine=True needs the default selection (policy='global', skip=0)")

@@ -28,6 +28,9 @@ device-resident pipeline:
 
 Parity protocol: batch b = global indices [b*B, (b+1)*B), unshuffled, so
 train-mode-BN EL2N scores are identical for any number of ranks.
+
+What consumes the EL2N forward (the logit scores, proto, nn) is forward_scores; the shard layout
+and the collectives are collectives; the method names are methods (all importable from here).
 """
 from __future__ import annotations
 
@@ -37,9 +40,15 @@ from typing import Dict, List, Optional, Sequence, Union
 
 import numpy as np
 import torch
-import torch.distributed as dist
 
 from . import _capi, el2n_fast, grand_fast
+from .collectives import (_all_reduce_sum, _world, all_shards, gather_padded,  # noqa: F401
+                          gather_rows, gather_scores, shard_bounds, shard_lengths, world_of)
+from .forward_scores import (ForwardScores, check_class_sizes,  # noqa: F401
+                             check_no_singleton_class, ensemble_mean, nearest_same_class)
+from .methods import (FEATURE_METHODS, FORWARD_FAMILY, FORWARD_SCORES,  # noqa: F401
+                      LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS, SELECT_POLICIES,
+                      check_selection, known, pass_of, refinable)
 from .resnet import ResNet
 
 MEAN = (0.4914, 0.4822, 0.4465)  # reference data/loader.py:10
@@ -128,7 +137,7 @@ class ScoreConfig:
     def __post_init__(self):
         self.methods = tuple(self.methods)
         for m in self.methods:
-            if m not in ("grand",) + FORWARD_SCORES:
+            if not known(m):
                 raise ValueError(f"unknown score method {m!r}")
         if self.select_by not in self.methods:
             raise ValueError(f"select_by={self.select_by!r} not among methods {self.methods}")
@@ -151,18 +160,11 @@ class ScoreConfig:
         if (self.refine_rel < 0 or self.refine_tol <= 0 or self.refine_groups < 1
                 or not 0 < self.refine_max_frac <= 1):
             raise ValueError("refine_rel >= 0, refine_tol > 0, refine_groups >= 1")
-        if self.select_policy not in SELECT_POLICIES:
-            raise ValueError(f"select_policy must be one of {SELECT_POLICIES} "
-                             f"(got {self.select_policy!r})")
-        if (isinstance(self.select_skip, bool)
-                or not isinstance(self.select_skip, (int, np.integer)) or self.select_skip < 0):
-            raise ValueError(f"select_skip must be an integer >= 0 (got {self.select_skip!r})")
-        self.select_skip = int(self.select_skip)
+        self.select_skip = check_selection(self.select_policy, self.select_skip)
         if self.refine is True and not self.default_selection():
             raise ValueError("refine=True needs the default selection (select_policy='global', "
                              "select_skip=0): the refinement re-scores around one threshold")
-        if self.refine is True and self.select_by in (LOGIT_METHODS + FEATURE_METHODS
-                                                      + NEIGHBOR_METHODS):
+        if self.refine is True and not refinable(self.select_by):
             raise ValueError(f"refine=True re-scores EL2N or GraNd only (select_by="
                              f"{self.select_by!r})")
         if self.el2n_chunk < self.batch_size:
@@ -171,107 +173,6 @@ class ScoreConfig:
 
     def default_selection(self) -> bool:
         return self.select_policy == "global" and self.select_skip == 0
-
-
-SELECT_POLICIES = ("global", "stratified", "balanced")
-
-# The logit scores beside EL2N (include/dd_capi.h dd_logit_scores): the mean over the K
-# checkpoints of the five single-forward statistics, and Dataset Cartography's variability, the
-# standard deviation of wrong_mass over the checkpoints.  Larger means harder for every one.
-LOGIT_METHODS = _capi.LOGIT_STATS + ("variability",)
-LOGIT_FAMILY = ("el2n",) + LOGIT_METHODS  # the scores of one train-BN forward per checkpoint
-# Scores of that forward's pooled feature rows f_i (the rows the classifier consumes):
-#   proto_i = || f_i - mu_{y_i} ||_2,  mu_c = the mean of f_i over the WHOLE dataset's class c
-# (Sorscher et al.'s prototypicality; larger = more atypical).  Not a function of one row: the
-# class means are summed in exact fixed point over chunks, lanes and ranks (include/dd_capi.h
-# dd_class_feature_sums), which keeps the scores bitwise independent of all three.
-FEATURE_METHODS = ("proto",)
-# everything the EL2N forward produces: one forward per checkpoint and chunk serves them all
-FORWARD_FAMILY = LOGIT_FAMILY + FEATURE_METHODS
-# Scores of a row against the other rows of its class, from the same feature rows:
-#   nn_i = min over j != i with y_j == y_i, over the WHOLE dataset, of || f_i - f_j ||_2
-# (the redundancy signal of SemDeDup and the density / coreset family: a near-duplicate scores
-# close to 0, so the default policy, which keeps the largest scores, drops duplicates first).
-NEIGHBOR_METHODS = ("nn",)
-# every score that comes from the EL2N forward
-FORWARD_SCORES = FORWARD_FAMILY + NEIGHBOR_METHODS
-
-
-def pass_of(method: str) -> str:
-    """The pass that computes `method`: "el2n" (the shared forward of the logit family and the
-    feature scores) or "grand"."""
-    return "el2n" if method in FORWARD_SCORES else "grand"
-
-
-def check_class_sizes(largest: int):
-    """The proto score's fixed-point class sums (|q| < 2^39 per element, int64) hold fewer than
-    2^24 members per class: reject a larger class."""
-    if largest >= _capi.PROTO_MAX_CLASS:
-        raise ValueError(f"proto: a class of {largest} members; the exact int64 feature sums "
-                         f"hold fewer than {_capi.PROTO_MAX_CLASS} (2^24) per class")
-
-
-def check_no_singleton_class(counts):
-    """The nn score of a class's only member would be infinite (no other row of its class):
-    reject a dataset with such a class, naming it.  counts: members per class over the whole
-    dataset (an empty class is fine)."""
-    for c, m in enumerate(counts):
-        if int(m) == 1:
-            raise ValueError(f"nn: class {c} has exactly one member in the whole dataset; its "
-                             f"nearest same-class neighbour does not exist (score +inf)")
-
-
-def shard_lengths(n: int, group=None):
-    """(rows per rank in rank order, this rank): one small all-gather, once per scoring call."""
-    world, rank = _world(group)
-    if world == 1:
-        return [int(n)], 0
-    dev = "cpu" if dist.get_backend(group) == "gloo" else torch.device("cuda",
-                                                                       torch.cuda.current_device())
-    parts = _all_gather_same(torch.tensor([int(n)], dtype=torch.int64, device=dev), group)
-    return [int(p.item()) for p in parts], rank
-
-
-def gather_rows(t: torch.Tensor, lengths, group=None) -> torch.Tensor:
-    """Every rank's rows [n_r, ...] in rank order -> [sum n_r, ...], one all-gather: the shards
-    are padded to the longest, as in gather_scores (gloo: staged through host memory).  With one
-    rank, `t` itself."""
-    if len(lengths) == 1:
-        return t
-    L = max(lengths)
-    buf = torch.zeros((L,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device)
-    buf[:t.shape[0]] = t
-    parts = _all_gather_same(buf, group)
-    return torch.cat([p[:m] for p, m in zip(parts, lengths)])
-
-
-def class_grouping(labels: torch.Tensor, num_classes: int):
-    """(order, offsets, counts, bad) of int64 device labels [n]: the rows stable-sorted by class
-    with the labels outside [0, C) last (past offsets[C]: in no class), the int64 [C + 1] class
-    offsets, and dd_class_counts' outputs."""
-    C = int(num_classes)
-    counts, bad = _capi.class_counts(labels, C, check=False)
-    key = torch.where((labels >= 0) & (labels < C), labels, torch.full_like(labels, C))
-    off = torch.zeros(C + 1, dtype=torch.int64, device=labels.device)
-    off[1:] = torch.cumsum(counts, 0)
-    return torch.argsort(key, stable=True), off, counts, bad
-
-
-def nearest_same_class(features: torch.Tensor, labels: torch.Tensor, num_classes: int,
-                       operands: str = "f16x3") -> torch.Tensor:
-    """fp32 [n]: each row's distance to the nearest other row of its class among `features`
-    [n, D] (one dd_nn_same_class launch; a tie goes to the smaller row index).  Raises
-    LabelError for a label outside [0, C) and ValueError for a class of exactly one member."""
-    labels = labels.contiguous()
-    order, off, counts, bad = class_grouping(labels, num_classes)
-    host = torch.cat([counts, bad.to(torch.int64)]).tolist()  # the one read of the counts
-    if host[-1]:
-        raise _capi.LabelError(f"nn: {host[-1]} label(s) outside [0, {int(num_classes)})")
-    check_no_singleton_class(host[:-1])
-    rows = features.index_select(0, order)
-    dist_sorted = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)
-    _capi.nn_same_class(rows, order, off, rows, order, off, operands=operands, dist=dist_sorted)
-    return torch.empty_like(dist_sorted).index_copy_(0, order, dist_sorted)
 
 
 def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
@@ -365,72 +266,6 @@ def normalize_refine(v) -> Union[bool, str]:
     raise ValueError(f"refine must be True, False or 'auto' (got {v!r})")
 
 
-def shard_bounds(n: int, batch_size: int, world: int, rank: int):
-    """Contiguous, batch-aligned shard [lo, hi) of rank `rank`:
-    rank r gets batches floor(r*nb/W) .. floor((r+1)*nb/W)-1 of nb = ceil(n/B)."""
-    if world <= 0 or not 0 <= rank < world:
-        raise ValueError("bad rank/world")
-    nb = -(-n // batch_size)
-    b_lo = (rank * nb) // world
-    b_hi = ((rank + 1) * nb) // world
-    return min(n, b_lo * batch_size), min(n, b_hi * batch_size)
-
-
-def all_shards(n: int, batch_size: int, world: int):
-    return [shard_bounds(n, batch_size, world, r) for r in range(world)]
-
-
-def gather_scores(local: torch.Tensor, n: int, batch_size: int, group=None) -> torch.Tensor:
-    """All-gather per-rank score shards into the full [n] vector (every rank gets it).
-
-    One collective: each rank contributes its shard padded to the longest shard; indices are
-    implicit in the shard bounds.  On GPU with the "nccl" backend this is RCCL over xGMI."""
-    if not dist.is_available() or not dist.is_initialized():
-        if local.numel() != n:
-            raise ValueError("single-process gather needs the whole score vector")
-        return local
-    world = dist.get_world_size(group)
-    bounds = all_shards(n, batch_size, world)
-    L = max(hi - lo for lo, hi in bounds)
-    buf = torch.zeros(L, dtype=local.dtype, device=local.device)
-    buf[:local.numel()] = local
-    if dist.get_backend(group) == "gloo":
-        # gloo (CPU tests; ranks sharing one GPU, where RCCL refuses a second communicator on
-        # the device): device shards are staged through host memory
-        host = buf.cpu()
-        parts = [torch.empty_like(host) for _ in range(world)]
-        dist.all_gather(parts, host, group=group)
-        flat = torch.cat(parts).to(local.device)
-    else:
-        flat = torch.empty(world * L, dtype=local.dtype, device=local.device)
-        dist.all_gather_into_tensor(flat, buf, group=group)
-    return torch.cat([flat[r * L: r * L + (hi - lo)] for r, (lo, hi) in enumerate(bounds)])
-
-
-def _all_gather_same(t: torch.Tensor, group=None):
-    """All-gather a same-shape tensor from every rank -> list in rank order (gloo: staged
-    through host memory, as gather_scores)."""
-    world = dist.get_world_size(group)
-    if dist.get_backend(group) == "gloo":
-        host = t.cpu()
-        parts = [torch.empty_like(host) for _ in range(world)]
-        dist.all_gather(parts, host, group=group)
-        return [p.to(t.device) for p in parts]
-    flat = torch.empty((world,) + tuple(t.shape), dtype=t.dtype, device=t.device)
-    dist.all_gather_into_tensor(flat, t.contiguous(), group=group)
-    return list(flat.unbind(0))
-
-
-def _all_reduce_sum(t: torch.Tensor, group=None):
-    """In-place sum over ranks (gloo: staged through host memory)."""
-    if dist.get_backend(group) == "gloo":
-        host = t.cpu()
-        dist.all_reduce(host, group=group)
-        t.copy_(host)
-    else:
-        dist.all_reduce(t, group=group)
-
-
 def chunk_plan(lo: int, hi: int, granule: int, chunk: int, even: bool = False):
     """Launch chunks [(c0, c1)] covering [lo, hi) in whole `granule`-row batches, and the
     buffer size.  Default: full `chunk`-row launches and one shorter tail, which runs at its
@@ -467,16 +302,6 @@ def chunk_plan(lo: int, hi: int, granule: int, chunk: int, even: bool = False):
 def run_rows(n: int, granule: int) -> int:
     """Rows a launch of n valid rows runs at: whole granules (pinned BN batches)."""
     return -(-n // granule) * granule
-
-
-def _world(group=None):
-    if dist.is_available() and dist.is_initialized():
-        return dist.get_world_size(group), dist.get_rank(group)
-    return 1, 0
-
-
-def world_of(group=None) -> int:
-    return _world(group)[0]
 
 
 def sharded_job(score_shard, n: int, batch_size: int, sparsity: float, select_by: str, select,
@@ -662,26 +487,23 @@ class ScoringEngine:
         # on bf16 halves (run(); the engine keeps bf16 GraNd packs from then on)
         self.grand_fallback: Optional[str] = None
         self.fallback: Dict[str, str] = {}  # method -> why it was re-scored on bf16 halves
-        self._bad = None  # dd_el2n's label counter of the current score_shard
+        self._bad = None  # the last score_shard's count of labels outside [0, C)
         # optional heartbeat, called with a short message every `progress_every` launch chunks
         # (a long config-5 pass otherwise prints nothing for minutes)
         self.progress = None
         self.progress_every = 100
-        self._side: Optional[torch.cuda.Stream] = None  # the concurrent pass stream
-        self._lane_streams: List[torch.cuda.Stream] = []
-        self._conv_meta = self._describe_convs(models[0])
+        self._lane_streams: List[torch.cuda.Stream] = []  # (the first: concurrent_passes')
+        self._check_convs(models[0])
 
     # ---- helpers ---------------------------------------------------------------------------
     @staticmethod
-    def _describe_convs(model: ResNet):
-        meta = {}
+    def _check_convs(model: ResNet):
         for name, mod in model.named_modules():
             if isinstance(mod, torch.nn.Conv2d):
                 if mod.groups != 1 or mod.bias is not None or mod.dilation != (1, 1):
                     raise ValueError(f"{name}: only dense, bias-free, undilated convs")
                 if mod.stride[0] != mod.stride[1] or mod.padding[0] != mod.padding[1]:
                     raise ValueError(f"{name}: asymmetric stride/padding unsupported")
-        return meta
 
     def _workspace(self, nbytes: int, lane: int = 0) -> torch.Tensor:
         ws = self._wss.get(lane)
@@ -698,116 +520,76 @@ class ScoringEngine:
             self.progress(f"{what} chunk {ci + 1}/{n}")
 
     # ---- passes ----------------------------------------------------------------------------
-    def _score_logits(self, model: ResNet, logits, labels, accum, r0, r1):
-        """One launch's logits into rows [r0, r1) of the logit family's accumulators.  `accum`
-        is the EL2N accumulator (a tensor), or {method: accumulator} over the requested family
-        members ("variability" holds Welford's M2 and "variability_mean" its mean): dd_el2n
-        runs only if el2n is among them, and one dd_logit_scores launch serves all the others.
-        The label counter of the pass goes to dd_el2n when it runs, else to dd_logit_scores,
-        so a row is counted once."""
-        if isinstance(accum, torch.Tensor):
-            accum = {"el2n": accum}
-        counter = self._counter("el2n", model)
-        if "el2n" in accum:
-            _capi.el2n(logits, labels, accum=accum["el2n"][r0:r1], bad_labels=counter)
-            counter = None
-        kw = {m: accum[m][r0:r1] for m in _capi.LOGIT_STATS if m in accum}
-        if "variability" in accum:
-            kw.update(var_mean=accum["variability_mean"][r0:r1],
-                      var_m2=accum["variability"][r0:r1],
-                      k=1 + next(i for i, m in enumerate(self.models) if m is model))
-        if kw:
-            _capi.logit_scores(logits, labels, bad_labels=counter, **kw)
+    def el2n_pass(self, model: ResNet, images_u8, labels, lo, hi, scores: ForwardScores,
+                  ckpt: int):
+        """Checkpoint `ckpt`'s train-BN forward over the shard, batch partition anchored at 0,
+        into `scores`: accum[j] += EL2N(x_{lo+j}), and the other forward scores."""
+        for _ in self._el2n_chunks(model, images_u8, labels, lo, hi, scores, ckpt):
+            pass
 
-    def el2n_pass(self, model: ResNet, images_u8, labels, lo, hi, accum):
-        """accum[j] += EL2N(x_{lo+j}) for the shard, batch partition anchored at 0 (accum: the
-        EL2N accumulator, or the logit family's accumulators: _score_logits).
+    def _el2n_chunks(self, model: ResNet, images_u8, labels, lo, hi, scores: ForwardScores,
+                     ckpt: int, lane=0, lanes=1):
+        """el2n_pass as a generator: chunks lane, lane + lanes, ... of the plan, yielding after
+        each (score_shard interleaves the lanes' chunks on their streams).  Every launch's logits
+        go to `scores.consume` and, where `scores.features` is a buffer, the same forward's
+        pooled feature rows are written there.  On the hand-scheduled
+        forward a chunk is `el2n_chunk` examples (whole pinned BN groups of batch_size); where
+        that forward does not apply, one pinned batch on model.run.
 
         A ragged final batch (N % B rows) is run padded to B rows with its BN statistics
         taken over the valid rows only (`n_valid`): identical scores, and MIOpen keeps the
         solvers it uses for full batches (at unusual batch sizes its immediate mode can fall
         back to naive kernels, SURVEY-era profile profiles/r01_v1)."""
-        B = self.cfg.batch_size
-        if (self.cfg.fast_el2n and self.cfg.fast_convs and self.cfg.el2n_bn == "batch"
-                and el2n_fast.applicable(model)):
-            return self._el2n_pass_grouped(model, images_u8, labels, lo, hi, accum)
-        xbuf = torch.zeros((B,) + tuple(images_u8.shape[1:]), dtype=torch.float32,
-                           device=self.device)
-        feats = self._feature_rows(accum)
-        with torch.inference_mode():
-            for b0 in range(lo, hi, B):
-                b1 = min(hi, b0 + B)
-                n = b1 - b0
-                pad = self.cfg.pad_ragged and n < B and self.cfg.el2n_bn == "batch"
-                x = self._normalize(images_u8[b0:b1], xbuf[:n])
-                if pad:
-                    xbuf[n:].zero_()
-                    x = xbuf
-                if feats is None:
-                    logits = model.run(x, bn=self.cfg.el2n_bn, n_valid=n if pad else None,
-                                       fast=self.cfg.fast_convs)
-                else:
-                    # the same one forward; its tape ends with the classifier's input rows
-                    tape = []
-                    logits = model.run(x, bn=self.cfg.el2n_bn, n_valid=n if pad else None,
-                                       fast=self.cfg.fast_convs, tape=tape)
-                    feats[b0 - lo:b1 - lo].copy_(tape[-1][1][:n])
-                    del tape
-                logits = logits[:n].float().contiguous()
-                self._score_logits(model, logits, labels[b0:b1], accum, b0 - lo, b1 - lo)
-
-    @staticmethod
-    def _feature_rows(accum) -> Optional[torch.Tensor]:
-        """The shard's feature buffer [n, D] among the forward family's targets (score_shard
-        puts it there when a feature score is requested), else None."""
-        return accum.get("proto_features") if isinstance(accum, dict) else None
-
-    def _el2n_pass_grouped(self, model: ResNet, images_u8, labels, lo, hi, accum):
-        """el2n_pass on the hand-scheduled forward: `el2n_chunk` examples (whole pinned BN
-        groups of batch_size) per launch; the tail chunk runs at full size, zero-padded, with
-        its statistics over the valid rows only."""
-        for _ in self._el2n_chunks(model, images_u8, labels, lo, hi, accum):
-            pass
-
-    def _el2n_chunks(self, model: ResNet, images_u8, labels, lo, hi, accum, lane=0, lanes=1):
-        """The grouped EL2N pass as a generator: chunks lane, lane + lanes, ... of the plan,
-        yielding after each (score_shard interleaves the lanes' chunks on their streams)."""
-        B = self.cfg.batch_size
-        even = self.cfg.even_chunks
-        plan, CH = chunk_plan(lo, hi, B, self.cfg.el2n_chunk, even)
+        cfg = self.cfg
+        B = cfg.batch_size
+        grouped = (cfg.fast_el2n and cfg.fast_convs and cfg.el2n_bn == "batch"
+                   and el2n_fast.applicable(model))
+        even = cfg.even_chunks and grouped
+        plan, CH = chunk_plan(lo, hi, B, cfg.el2n_chunk if grouped else B, even)
         if len(plan) <= lane:
             return
+        padded = grouped or (cfg.pad_ragged and cfg.el2n_bn == "batch")
         # (a normal tensor, and inference mode per chunk: a context held across a yield would
         # leak into the other lanes' interleaved chunks)
         xbuf = torch.zeros((CH,) + tuple(images_u8.shape[1:]), dtype=torch.float32,
                            device=self.device)
-        feats = self._feature_rows(accum)
+        feats = scores.features
         for ci in range(lane, len(plan), lanes):
             b0, b1 = plan[ci]
             self._beat("el2n", ci, len(plan))
             n = b1 - b0
-            nr = CH if even else run_rows(n, B)  # whole pinned batches (a ragged one padded)
+            # whole pinned batches (a ragged one padded)
+            nr = CH if even else run_rows(n, B) if padded else n
             with torch.inference_mode():
                 xb = xbuf[:nr]
                 if n < nr:
                     xb[n:].zero_()
                 self._normalize(images_u8[b0:b1], xb[:n])
-                if feats is None:
-                    logits = el2n_fast.forward_logits(model, xb, B, n)[:n]
+                if not grouped:
+                    # the same one forward; its tape ends with the classifier's input rows
+                    tape = None if feats is None else []
+                    logits = model.run(xb, bn=cfg.el2n_bn, n_valid=n if n < nr else None,
+                                       fast=cfg.fast_convs, tape=tape)
+                    f = tape and tape[-1][1]
+                elif feats is None:
+                    logits = el2n_fast.forward_logits(model, xb, B, n)
                 else:
-                    # only the valid rows reach the feature buffer (never a ragged chunk's padding)
                     logits, f = el2n_fast.forward_features(model, xb, B, n)
+                if feats is not None:
+                    # only the valid rows reach the feature buffer (never a ragged chunk's padding)
                     feats[b0 - lo:b1 - lo].copy_(f[:n])
-                    logits = logits[:n]
-                self._score_logits(model, logits, labels[b0:b1], accum, b0 - lo, b1 - lo)
+                scores.consume(ckpt, logits[:n].float().contiguous(), labels[b0:b1], b0 - lo,
+                               b1 - lo)
             yield
 
-    def grand_pass(self, model: ResNet, images_u8, labels, lo, hi, accum):
-        for _ in self._grand_chunks(model, images_u8, labels, lo, hi, accum):
+    def grand_pass(self, model: ResNet, images_u8, labels, lo, hi, accum, counter=None):
+        for _ in self._grand_chunks(model, images_u8, labels, lo, hi, accum, counter):
             pass
 
-    def _grand_chunks(self, model: ResNet, images_u8, labels, lo, hi, accum, lane=0, lanes=1):
-        """accum[j] += ||grad_W CE(x_{lo+j})|| (eval-mode BN, Conv2d + Linear weights).
+    def _grand_chunks(self, model: ResNet, images_u8, labels, lo, hi, accum, counter=None,
+                      lane=0, lanes=1):
+        """accum[j] += ||grad_W CE(x_{lo+j})|| (eval-mode BN, Conv2d + Linear weights);
+        `counter`: the label counter, where this pass is the one that counts (score_shard).
 
         Chunks come from chunk_plan: whole `batch_size` granules, `grand_batch` rows each and
         a shorter tail run at its own size (whole granules; the padded rows discarded), so the
@@ -845,7 +627,7 @@ class ScoringEngine:
             bn_pairs = [] if self.cfg.grand_params == "all" else None
             if fused:
                 pairs, feat = grand_fast.forward_backward(
-                    model, x, lab, e, bn_pairs, bad_labels=self._counter("grand", model))
+                    model, x, lab, e, bn_pairs, bad_labels=counter)
                 work = [(m, inp, g, scale) for (m, inp, g, scale) in pairs]
                 lin = model.linear
             elif bn_pairs is not None:
@@ -858,7 +640,7 @@ class ScoringEngine:
                 with torch.enable_grad():
                     logits = model.run(xin, bn=bn, tape=tape, fast=self.cfg.fast_convs)
                     _capi.el2n(logits.detach().float().contiguous(), lab, e=e,
-                               bad_labels=self._counter("grand", model))
+                               bad_labels=counter)
                     convs = [t for t in tape if isinstance(t[0], torch.nn.Conv2d)]
                     grads = torch.autograd.grad(logits, [t[2] for t in convs], grad_outputs=e)
                 work = [(m, inp, g, scale) for (m, inp, _, scale), g in zip(convs, grads)]
@@ -886,10 +668,39 @@ class ScoringEngine:
     def _lanes_apply(self) -> bool:
         """Lanes interleave the chunk generators of the hand-scheduled passes."""
         c = self.cfg
-        el2n_ok = not any(m in FORWARD_SCORES for m in c.methods) or (
+        return "el2n" not in map(pass_of, c.methods) or (
             c.fast_el2n and c.fast_convs and c.el2n_bn == "batch"
             and all(el2n_fast.applicable(m) for m in self.models))
-        return el2n_ok
+
+    def _streams(self, count: int) -> List[torch.cuda.Stream]:
+        while len(self._lane_streams) < count:
+            self._lane_streams.append(torch.cuda.Stream(self.device))
+        return self._lane_streams[:count]
+
+    @staticmethod
+    def _run(kinds, K, chunks, fwd: ForwardScores, streams):
+        """The passes of `kinds`, checkpoint by checkpoint, each checkpoint's launch chunks
+        dealt to `streams` (the lanes; one stream: everything in order on it)."""
+        lanes = len(streams)
+        for kind in kinds:
+            for ckpt in range(K):
+                its = [chunks(kind, ckpt, j, lanes) for j in range(lanes)]
+                live = list(range(lanes))
+                while live:  # one chunk per lane in turn, each on its lane's stream
+                    for j in list(live):
+                        with torch.cuda.stream(streams[j]):
+                            if next(its[j], StopIteration) is StopIteration:
+                                live.remove(j)
+                if kind == "el2n" and fwd.features is not None:
+                    # on lane 0's stream, after every lane's last chunk of this checkpoint;
+                    # the next checkpoint's chunks, which overwrite the feature buffer,
+                    # wait for the distance launch (stream waits, no host sync)
+                    for st in streams[1:]:
+                        streams[0].wait_stream(st)
+                    with torch.cuda.stream(streams[0]):
+                        fwd.end_checkpoint()
+                    for st in streams[1:]:
+                        st.wait_stream(streams[0])
 
     def score_shard(self, images_u8: torch.Tensor, labels: torch.Tensor, lo: int, hi: int,
                     check: bool = True, group=None) -> Dict[str, torch.Tensor]:
@@ -900,255 +711,73 @@ class ScoringEngine:
         range).  run() passes check=False and checks the gathered vectors instead (_validate),
         so that on W > 1 ranks every rank raises (or falls back) together.
 
-        "proto" is the one score for which a shard is not a slice of the whole: its class
-        prototypes are means over every rank's rows.  run() passes its process `group`, and
-        the fixed-point class sums (and, once per call, the class counts) are all-reduced over
-        it, one collective per checkpoint, issued by every rank in the same order.  A direct
-        call without a group takes the prototypes over [lo, hi) only.
-
-        "nn" is the other one: a row's nearest neighbour may lie on another rank.  With the
-        `group`, the shard labels are all-gathered once per call and the feature rows once per
-        checkpoint (every rank in the same order), and each rank searches its own rows among
-        the whole dataset's.  A direct call without a group searches [lo, hi) only."""
+        "proto" and "nn" are the scores for which a shard is not a slice of the whole: the class
+        prototypes are means over every rank's rows, and a row's nearest neighbour may lie on
+        another rank.  run() passes its process `group`, over which forward_scores issues their
+        collectives; a direct call without a group takes both over [lo, hi) only."""
         n = hi - lo
         K = len(self.models)
+        cfg = self.cfg
+        kinds = list(dict.fromkeys(pass_of(m) for m in cfg.methods))  # first-use order
+        # labels outside [0, C) are counted on the first pass over the shard only (the first
+        # method's first checkpoint scores every row once), so the count is of rows, not of
+        # row-passes: by the forward scores if that pass is EL2N's, else by GraNd's kernels
         self._bad = _capi.label_counter(self.device)
-        # counted on the first pass over the shard only (the first method's first checkpoint
-        # scores every row once), so the count is of rows, not of row-passes
-        self._bad_pass = (pass_of(self.cfg.methods[0]), self.models[0])
-        accs = {m: torch.zeros(n, dtype=torch.float32, device=self.device)
-                for m in self.cfg.methods}
-        # everything the EL2N forward produces (the logit family: el2n + LOGIT_METHODS, and the
-        # feature scores) shares one forward per checkpoint and chunk: its pass takes all the
-        # requested members' accumulators at once (_score_logits; proto_phase below)
-        family = {m: accs[m] for m in self.cfg.methods if m in FORWARD_SCORES}
-        if "variability" in family:  # accs["variability"] is Welford's M2, this is its mean
-            family["variability_mean"] = torch.zeros_like(accs["variability"])
-        proto = self._proto_setup(labels[lo:hi], family, group) if "proto" in family else None
-        nn = self._nn_setup(labels[lo:hi], family, group) if "nn" in family else None
-        # the buffers of the second phase, for the streams' bookkeeping below
-        phase_state = (list(proto.values()) if proto is not None else []) + [
-            t for t in (nn.values() if nn is not None else ()) if isinstance(t, torch.Tensor)]
-        kinds = list(dict.fromkeys(pass_of(m) for m in self.cfg.methods))  # first-use order
-        targets = {"el2n": family, "grand": accs.get("grand")}
-        buffers = {"el2n": list(family.values()), "grand": [accs.get("grand")]}
+        # everything the EL2N forward produces shares one forward per checkpoint and chunk
+        fwd = ForwardScores(cfg, labels[lo:hi], self.models[0].linear, group,
+                            counter=self._bad if kinds[0] == "el2n" else None)
+        grand = (torch.zeros(n, dtype=torch.float32, device=self.device)
+                 if "grand" in kinds else None)
 
-        def proto_phase():
-            """The second phase of a checkpoint with proto requested, on the current stream,
-            after every chunk of the checkpoint has written its feature rows: one sums launch
-            over the shard, one all-reduce, the centroids, one distance launch."""
-            sums, bad_feat = proto["sums"], proto["bad_feat"]
-            C, D = sums.shape
-            proto["reduce"].zero_()
-            bad_feat.zero_()
-            _capi.class_feature_sums(proto["features"], proto["labels"], sums, bad_feat,
-                                     order=proto["order"])
-            if world_of(group) > 1:
-                # one int64 buffer: the sums, then the per-class counts of unrepresentable rows
-                proto["reduce"][C * D:].copy_(bad_feat)
-                _all_reduce_sum(proto["reduce"], group)
-                bad_feat.copy_(proto["reduce"][C * D:])
-            _capi.class_centroids(sums, proto["counts"], bad_feat, out=proto["centroids"])
-            _capi.proto_scores(proto["features"], proto["labels"], proto["centroids"],
-                               accum=accs["proto"])
+        def chunks(kind, ckpt, lane=0, lanes=1):
+            """Checkpoint `ckpt`'s pass of `kind`: the generator over its launch chunks lane,
+            lane + lanes, ..."""
+            model = self.models[ckpt]
+            if kind == "el2n":
+                return self._el2n_chunks(model, images_u8, labels, lo, hi, fwd, ckpt, lane, lanes)
+            counter = self._bad if kinds[0] == "grand" and ckpt == 0 else None
+            return self._grand_chunks(model, images_u8, labels, lo, hi, grand, counter, lane,
+                                      lanes)
 
-        def nn_phase():
-            """The same point of a checkpoint with nn requested: one all-gather of the feature
-            rows (world > 1), the rows gathered into class order, one dd_nn_same_class launch
-            that accumulates in class order (scattered back to shard order after the last
-            checkpoint)."""
-            feats = nn["features"]
-            torch.index_select(feats, 0, nn["q_order"], out=nn["q"])
-            allf = gather_rows(feats, nn["lengths"], group)
-            if allf is feats:
-                cand = nn["q"]  # one rank: the candidates are the queries
-            else:
-                cand = torch.index_select(allf, 0, nn["c_order"], out=nn["c"])
-            nn["workspace"] = _capi.nn_same_class(
-                nn["q"], nn["q_id"], nn["q_off"], cand, nn["c_id"], nn["c_off"],
-                operands=self.cfg.el2n_operands, accum=nn["accum"], workspace=nn["workspace"])
-
-        def second_phase():
-            if proto is not None:
-                proto_phase()
-            if nn is not None:
-                nn_phase()
-
-        def passes(kind):
-            for model in self.models:
-                if kind == "el2n":
-                    self.el2n_pass(model, images_u8, labels, lo, hi, family)
-                    second_phase()
-                else:
-                    self.grand_pass(model, images_u8, labels, lo, hi, accs["grand"])
-
-        lanes = self.cfg.lanes
-        if lanes > 1 and self._lanes_apply():
-            main = torch.cuda.current_stream(self.device)
-            while len(self._lane_streams) < lanes:
-                self._lane_streams.append(torch.cuda.Stream(self.device))
-            streams = self._lane_streams[:lanes]
-            for st in streams:
-                st.wait_stream(main)  # inputs and accumulators are ready on the main stream
-            for kind in kinds:
-                gen = self._el2n_chunks if kind == "el2n" else self._grand_chunks
-                for model in self.models:
-                    its = [gen(model, images_u8, labels, lo, hi, targets[kind], lane=j,
-                               lanes=lanes) for j in range(lanes)]
-                    live = list(range(lanes))
-                    while live:  # one chunk per lane in turn, each on its lane's stream
-                        for j in list(live):
-                            with torch.cuda.stream(streams[j]):
-                                if next(its[j], StopIteration) is StopIteration:
-                                    live.remove(j)
-                    if kind == "el2n" and phase_state:
-                        # on lane 0's stream, after every lane's last chunk of this checkpoint;
-                        # the next checkpoint's chunks, which overwrite the feature buffer,
-                        # wait for the distance launch (stream waits, no host sync)
-                        for st in streams[1:]:
-                            streams[0].wait_stream(st)
-                        with torch.cuda.stream(streams[0]):
-                            second_phase()
-                        for st in streams[1:]:
-                            st.wait_stream(streams[0])
-            for t in phase_state:
-                for st in streams:
-                    t.record_stream(st)
-            for st in streams:
-                for kind in kinds:
-                    for acc in buffers[kind]:
-                        acc.record_stream(st)
-                main.wait_stream(st)
-        elif self.cfg.concurrent_passes and len(kinds) > 1:
-            main = torch.cuda.current_stream(self.device)
-            if self._side is None:
-                self._side = torch.cuda.Stream(self.device)
-            side = self._side
-            side.wait_stream(main)  # inputs and accumulators are ready on the main stream
-            with torch.cuda.stream(side):
-                passes(kinds[0])
-            for acc in buffers[kinds[0]] + (phase_state if kinds[0] == "el2n" else []):
-                acc.record_stream(side)
-            for kind in kinds[1:]:
-                passes(kind)
-            main.wait_stream(side)
+        # the stream modes: which passes run on which streams (the lanes, or the second stream
+        # of concurrent_passes, fork from the current stream and join it again)
+        main = torch.cuda.current_stream(self.device)
+        if cfg.lanes > 1 and self._lanes_apply():
+            modes = [(kinds, self._streams(cfg.lanes))]
+        elif cfg.concurrent_passes and len(kinds) > 1:
+            modes = [(kinds[:1], self._streams(1)), (kinds[1:], [main])]
         else:
-            for kind in kinds:
-                passes(kind)
-        if nn is not None:  # class order -> shard order
-            accs["nn"].index_copy_(0, nn["q_order"], nn["accum"])
-        out = {}
-        for method in self.cfg.methods:
-            res = torch.empty_like(accs[method])
-            if method == "variability":
-                _capi.variability_finalize(accs[method], K, res)
-            else:
-                _capi.ensemble_finalize(accs[method], K, res)
-            out[method] = res
+            modes = [(kinds, [main])]
+        for ks, streams in modes:
+            for st in streams:
+                if st != main:
+                    st.wait_stream(main)  # inputs and accumulators are ready on the main stream
+            self._run(ks, K, chunks, fwd, streams)
+        for ks, streams in modes:
+            used = (fwd.tensors() if "el2n" in ks else []) + ([grand] if "grand" in ks else [])
+            for st in streams:
+                if st != main:
+                    for t in used:
+                        t.record_stream(st)
+                    main.wait_stream(st)
+        done = fwd.finalize(K)
+        if grand is not None:
+            done["grand"] = ensemble_mean(grand, K)
+        out = {m: done[m] for m in cfg.methods}  # (run() gathers the vectors in this order)
         if check and n:
             _capi.check_labels(self._bad, self.models[0].linear.out_features, "score_shard")
-            fin = torch.stack([torch.isfinite(out[m]).all() for m in self.cfg.methods]).cpu()
-            for m, ok in zip(self.cfg.methods, fin.tolist()):
+            fin = torch.stack([torch.isfinite(out[m]).all() for m in cfg.methods]).cpu()
+            for m, ok in zip(cfg.methods, fin.tolist()):
                 if not ok:
                     # e.g. an activation past fp16's range (65504) in a forward on fp16 operand
                     # halves: fail loudly rather than return non-finite scores (run() re-scores
                     # on bf16 halves by itself)
-                    ops = "el2n_operands" if m in FORWARD_SCORES else "grand_operands"
+                    ops = f"{pass_of(m)}_operands"
                     raise ValueError(f"non-finite {m} scores" + (
                         f": an activation of the forward may have left fp16's range; score "
                         f"with {ops}='bf16x3' (ScoreConfig), or through run(), which falls "
                         f"back to bf16 halves by itself" if self._f16_forward(m) else ""))
         return out
-
-    def _proto_setup(self, labels: torch.Tensor, family: dict, group) -> Dict[str, torch.Tensor]:
-        """The per-call state of the proto score for the shard's `labels` [n], allocated once and
-        reused by every checkpoint: the [n, D] fp32 feature buffer (n D 4 bytes: 102 MB at
-        50 000 x 512, 10.5 GB for 1.28 M x 2048 rows on one rank; also put among the forward's
-        targets, where the chunks find it), the rows' order sorted by label, the class counts
-        over every rank (dd_class_counts + one all-reduce: labels do not change across
-        checkpoints), and the int64 buffer [C D + C] that is all-reduced per checkpoint."""
-        n = labels.numel()
-        lin = self.models[0].linear
-        C, D = lin.out_features, lin.in_features
-        if D > _capi.PROTO_MAX_D:
-            raise ValueError(f"proto: feature width {D} above {_capi.PROTO_MAX_D}")
-        labels = labels.contiguous()
-        world = world_of(group)
-        counts, bad = _capi.class_counts(labels, C, check=False)
-        if world > 1:
-            _all_reduce_sum(counts, group)
-        if (self._bad_pass[0] == "el2n"
-                and not any(m in LOGIT_FAMILY for m in self.cfg.methods)):
-            self._bad.add_(bad)  # no logit kernel runs to count the labels outside [0, C)
-        # the fixed-point sums hold fewer than 2^24 members per class; the shards are balanced
-        # to within a batch, so the counts are read back only where the set could be that large
-        if world * (n + self.cfg.batch_size) >= _capi.PROTO_MAX_CLASS:
-            check_class_sizes(int(counts.max().item()))
-        dev = self.device
-        reduce = torch.zeros(C * D + C, dtype=torch.int64, device=dev)
-        state = {
-            "features": torch.empty((n, D), dtype=torch.float32, device=dev),
-            "labels": labels,
-            "order": torch.argsort(labels, stable=True),
-            "counts": counts,
-            "reduce": reduce,
-            "sums": reduce[:C * D].view(C, D),
-            "bad_feat": torch.zeros(C, dtype=torch.int32, device=dev),
-            "centroids": torch.empty((C, D), dtype=torch.float32, device=dev),
-        }
-        family["proto_features"] = state["features"]
-        return state
-
-    def _nn_setup(self, labels: torch.Tensor, family: dict, group) -> dict:
-        """The per-call state of the nn score for the shard's `labels` [n], built once and reused
-        by every checkpoint (labels do not change across checkpoints): the [n, D] feature buffer
-        (proto's when both are requested), every rank's labels (one all-gather), the class
-        offsets of the whole dataset and of this shard (dd_class_counts), the class-sorted order
-        of the candidates (all rows) and of the queries (this rank's rows) with their global ids,
-        the class-ordered row buffers, the class-ordered accumulator and the kernel's workspace
-        (4 (n + N) pad16(D) bytes).  The whole dataset's counts are read to the host once: a
-        class of exactly one member is rejected by name."""
-        n = labels.numel()
-        lin = self.models[0].linear
-        C, D = lin.out_features, lin.in_features
-        if D > _capi.PROTO_MAX_D:
-            raise ValueError(f"nn: feature width {D} above {_capi.PROTO_MAX_D}")
-        dev = self.device
-        labels = labels.contiguous()
-        lengths, rank = shard_lengths(n, group)
-        all_labels = gather_rows(labels, lengths, group)
-        base = sum(lengths[:rank])
-
-        q_order, q_off, counts, bad = class_grouping(labels, C)
-        if all_labels is labels:
-            c_order, c_off = q_order, q_off
-        else:
-            c_order, c_off, counts, _ = class_grouping(all_labels.contiguous(), C)
-        if (self._bad_pass[0] == "el2n"
-                and not any(m in FORWARD_FAMILY for m in self.cfg.methods)):
-            self._bad.add_(bad)  # neither a logit kernel nor proto counts the bad labels
-        check_no_singleton_class(counts.tolist())  # the one read of the counts
-        N = all_labels.numel()
-        feats = family.get("proto_features")
-        if feats is None:
-            feats = torch.empty((n, D), dtype=torch.float32, device=dev)
-            family["proto_features"] = feats  # where the chunks find the feature buffer
-        need = _capi.nn_workspace_bytes(n, N, D, self.cfg.el2n_operands)
-        return {
-            "features": feats, "lengths": lengths,
-            "q_order": q_order, "q_off": q_off, "q_id": q_order + base,
-            "c_order": c_order, "c_off": c_off, "c_id": c_order,
-            "q": torch.empty((n, D), dtype=torch.float32, device=dev),
-            "c": (torch.empty((N, D), dtype=torch.float32, device=dev)
-                  if all_labels is not labels else None),
-            "accum": torch.zeros(n, dtype=torch.float32, device=dev),
-            "workspace": torch.empty(max(need, 1), dtype=torch.uint8, device=dev),
-        }
-
-    def _counter(self, method: str, model) -> Optional[torch.Tensor]:
-        """dd_el2n's label counter for the pass (method, model), or None (see score_shard)."""
-        bp = getattr(self, "_bad_pass", None)
-        return self._bad if bp is not None and bp[0] == method and bp[1] is model else None
 
     def _validate(self, full, score, N, B, group):
         """run()'s check of the gathered score vectors (sharded_job's `validate`), before the
@@ -1183,14 +812,13 @@ class ScoringEngine:
             _all_reduce_sum(bad, group)
         _capi.check_labels(bad, self.models[0].linear.out_features, "run")
         redo = [m for i, m in enumerate(ms) if not bool(fin[i]) and self._f16_forward(m)]
-        if any(m in FORWARD_SCORES for m in redo):
+        if "el2n" in map(pass_of, redo):
             # the logit family shares its forward: the whole requested family is re-scored, in
             # one forward per checkpoint again
-            redo = [m for m in ms if m in FORWARD_SCORES or m in redo]
+            redo = [m for m in ms if pass_of(m) == "el2n" or m in redo]
         if redo:
-            ops = {"el2n": "el2n_operands", "grand": "grand_operands"}
             self.cfg = dataclasses.replace(self.cfg,
-                                           **{ops[pass_of(m)]: "bf16x3" for m in redo})
+                                           **{f"{pass_of(m)}_operands": "bf16x3" for m in redo})
             self.fallback.update({m: "a forward activation left fp16's range: re-scored on "
                                      "bf16 operand halves" for m in redo})
             if "grand" in redo:
@@ -1222,7 +850,7 @@ class ScoringEngine:
         c = self.cfg
         if not c.fast_convs:
             return False
-        if method in FORWARD_SCORES:  # one forward for the whole family
+        if pass_of(method) == "el2n":  # one forward for the whole family
             return c.el2n_operands == "f16x3"
         return c.grand_operands == "f16x3" and c.fold_bn
 
@@ -1253,10 +881,6 @@ class ScoringEngine:
 
         def select(keys, k):
             c = self.cfg
-            if c.default_selection():
-                self.last_selection = {"policy": "global", "skip": 0, "class_counts": None,
-                                       "class_skip": None, "class_quota": None}
-                return _capi.select_topk(keys, k, check_nan=check_nan)[0]
             all_labels = labels
             if c.select_policy != "global" and n_total is not None:
                 # each rank holds its shard's labels: the class policies' one extra collective
@@ -1282,8 +906,7 @@ class ScoringEngine:
         c = self.cfg
         if c.refine is False or not c.default_selection():
             return False
-        # the refinement re-scores EL2N and GraNd only
-        if method in LOGIT_METHODS + FEATURE_METHODS + NEIGHBOR_METHODS:
+        if not refinable(method):
             return False
         if method == "el2n":
             if c.refine == "auto" and c.el2n_operands == "f16x3":
@@ -1357,18 +980,11 @@ class ScoringEngine:
             per_rank = [[(r0, r1) for (r0, r1) in part_rows if blo <= r0 < bhi]
                         for blo, bhi in all_shards(N, B, world)]
             counts = [sum(r1 - r0 for r0, r1 in pr) for pr in per_rank]
-            L = max(counts)
-            shape = tuple(images_u8.shape[1:])
-            img = torch.zeros((L,) + shape, dtype=images_u8.dtype, device=self.device)
-            lab = torch.zeros(L, dtype=labels.dtype, device=self.device)
-            c = 0
-            for r0, r1 in per_rank[rank]:
-                img[c:c + r1 - r0] = images_u8[r0 - off:r1 - off]
-                lab[c:c + r1 - r0] = labels[r0 - off:r1 - off]
-                c += r1 - r0
-            img_all = torch.cat([t[:n] for t, n in zip(_all_gather_same(img, group), counts)])
-            lab_all = torch.cat([t[:n] for t, n in zip(_all_gather_same(lab, group), counts)])
-            del img, lab
+            own = [slice(r0 - off, r1 - off) for r0, r1 in per_rank[rank]]  # (may be none)
+            img_all = gather_padded(torch.cat([images_u8[:0]] + [images_u8[r] for r in own]),
+                                    counts, group)
+            lab_all = gather_padded(torch.cat([labels[:0]] + [labels[r] for r in own]),
+                                    counts, group)
             # rows ascend and the shards are contiguous and ascending: rank order is row order
             local, c = [], 0
             for r0, r1 in part_rows:
@@ -1384,9 +1000,7 @@ class ScoringEngine:
             acc = torch.zeros(c, dtype=torch.float32, device=self.device)
             for kk in range(K):  # checkpoint order, as the one-rank accumulation
                 acc += per[kk]
-            out = torch.empty_like(acc)
-            _capi.ensemble_finalize(acc, K, out)
-            outs.append(out)
+            outs.append(ensemble_mean(acc, K))
         return torch.cat(outs)
 
     def _rescore_fp32(self, method, images_u8, labels, rows, off, N, models=None,
@@ -1397,57 +1011,39 @@ class ScoringEngine:
         accumulation adds) of the ensemble mean over all K."""
         K = len(self.models)
         models = self.models if models is None else models
+
+        def ensemble(m, score_into):
+            """One launch's m rows: score_into(model, accumulator) over the models."""
+            accs = [torch.zeros(m, dtype=torch.float32, device=self.device)
+                    for _ in (models if per_ckpt else [None])]
+            for i, model in enumerate(models):
+                score_into(model, accs[i if per_ckpt else 0])
+            return torch.stack(accs) if per_ckpt else ensemble_mean(accs[0], K)
+
         if method == "grand":
             idx = torch.tensor([r0 - off for r0, _ in rows], dtype=torch.int64,
                                device=self.device)
             img, lab = images_u8[idx].contiguous(), labels[idx].contiguous()
             m = idx.numel()
-            accs = [torch.zeros(m, dtype=torch.float32, device=self.device)
-                    for _ in (models if per_ckpt else [None])]
             saved = self.cfg
             self.cfg = dataclasses.replace(saved, fast_convs=False, fused_grand=False,
                                            pegrad_precision="fp32", refine=False)
             try:
-                for i, model in enumerate(models):
-                    self.grand_pass(model, img, lab, 0, m, accs[i if per_ckpt else 0])
+                return ensemble(m, lambda model, acc: self.grand_pass(model, img, lab, 0, m, acc))
             finally:
                 self.cfg = saved
-            if per_ckpt:
-                return torch.stack(accs)
-            acc = accs[0]
-            out = torch.empty_like(acc)
-            _capi.ensemble_finalize(acc, K, out)
-            return out
-        # EL2N: whole pinned batches, `refine_groups` per launch (the count padded to a power of
-        # two, so MIOpen sees few distinct batch sizes), ragged last batch last
+        # EL2N: whole pinned batches, `refine_groups` per launch, ragged last batch last
         B = self.cfg.batch_size
         outs = []
-        step = self.cfg.refine_groups
-        shape = tuple(images_u8.shape[1:])
+
+        def fill(dst, r0, r1):
+            self._normalize(images_u8[r0 - off:r1 - off], dst)
+            return labels[r0 - off:r1 - off].to(torch.int64)
+
         with torch.inference_mode():
-            for c in range(0, len(rows), step):
-                part = rows[c:c + step]
-                G = 1 << (len(part) - 1).bit_length()
-                x = torch.zeros((G * B,) + shape, dtype=torch.float32, device=self.device)
-                lab = torch.zeros(G * B, dtype=torch.int64, device=self.device)
-                sel = []
-                for gi, (r0, r1) in enumerate(part):
-                    self._normalize(images_u8[r0 - off:r1 - off], x[gi * B:gi * B + (r1 - r0)])
-                    lab[gi * B:gi * B + (r1 - r0)] = labels[r0 - off:r1 - off]
-                    sel.append(torch.arange(gi * B, gi * B + (r1 - r0), device=self.device))
-                sel = torch.cat(sel)
-                r0, r1 = part[-1]
-                n_valid = (len(part) - 1) * B + (r1 - r0)
-                accs = [torch.zeros(sel.numel(), dtype=torch.float32, device=self.device)
-                        for _ in (models if per_ckpt else [None])]
-                for i, model in enumerate(models):
-                    logits = el2n_fast.forward_logits_fp32(model, x, B, n_valid)
-                    _capi.el2n(logits[sel].float().contiguous(), lab[sel].contiguous(),
-                               accum=accs[i if per_ckpt else 0])
-                if per_ckpt:
-                    outs.append(torch.stack(accs))
-                    continue
-                out = torch.empty_like(accs[0])
-                _capi.ensemble_finalize(accs[0], K, out)
-                outs.append(out)
+            for x, sel, n_valid, lab in el2n_fast.fp32_group_launches(
+                    rows, self.cfg.refine_groups, B, images_u8.shape[1:], self.device, fill):
+                outs.append(ensemble(sel.numel(), lambda model, acc: _capi.el2n(
+                    el2n_fast.forward_logits_fp32(model, x, B, n_valid)[sel].float().contiguous(),
+                    lab, accum=acc)))
         return torch.cat(outs, dim=-1)

@@ -58,6 +58,50 @@ def test_gloo_gather_select_equals_single_process(tmp_path, world, n):
         assert np.array_equal(o[n:].astype(np.int64), want_kept)
 
 
+PADDED_LENGTHS = [5, 0, 3]  # rows per rank: one longest, one empty, one shorter
+
+
+def _padded_parts(rank):
+    """What rank `rank` contributes to the gather_padded test: int64 [n_r] and fp32 [n_r, 4],
+    filled from the rank number."""
+    m = PADDED_LENGTHS[rank]
+    ids = 100 * rank + torch.arange(m, dtype=torch.int64)
+    return ids, (ids.to(torch.float32)[:, None] + torch.tensor([0.0, 0.25, 0.5, 0.75])) / 3
+
+
+def _padded_worker(rank, world, port, n, out_dir):
+    from data_diet_distributed_amd.collectives import gather_padded
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        ids, rows = _padded_parts(rank)
+        lo, hi = shard_bounds(n, 128, world, rank)
+        np.savez(os.path.join(out_dir, f"p{rank}.npz"),
+                 ids=gather_padded(ids, PADDED_LENGTHS).numpy(),
+                 rows=gather_padded(rows, PADDED_LENGTHS).numpy(),
+                 scores=gather_scores(torch.from_numpy(_score(np.arange(lo, hi))), n, 128).numpy())
+    finally:
+        dist.destroy_process_group()
+
+
+def test_gloo_gather_padded(tmp_path):
+    """gather_padded over ranks of 5, 0 and 3 rows: every rank gets the 8 rows in rank order,
+    bitwise what one process concatenates, 1-D and 2-D; and gather_scores (n = 1000, B = 128:
+    shards of 256, 384 and 360) returns the whole vector."""
+    world, n = 3, 1000
+    mp.spawn(_padded_worker, args=(world, _free_port(), n, str(tmp_path)), nprocs=world,
+             join=True)
+    ids, rows = (torch.cat(p).numpy() for p in zip(*map(_padded_parts, range(world))))
+    assert ids.shape == (8,) and rows.shape == (8, 4)
+    for r in range(world):
+        got = np.load(tmp_path / f"p{r}.npz")
+        assert got["ids"].dtype == np.int64 and got["rows"].dtype == np.float32
+        assert got["ids"].shape == (8,) and np.array_equal(got["ids"], ids)
+        assert got["rows"].shape == (8, 4) and got["rows"].tobytes() == rows.tobytes()
+        assert got["scores"].tobytes() == _score(np.arange(n)).tobytes()
+
+
 def _job_worker(rank, world, port, n, out_dir):
     """One rank of the real orchestration (`scoring.sharded_job`, the body of
     ScoringEngine.run): builds ONLY its shard of the synthetic set, scores it with the CPU

@@ -12,8 +12,8 @@ import numpy as np
 import pytest
 import torch
 
-from data_diet_distributed_amd import _capi, checkpoints, el2n_fast, score, scoring, subset_index
-from data_diet_distributed_amd import synthetic
+from data_diet_distributed_amd import _capi, checkpoints, el2n_fast, forward_scores, score
+from data_diet_distributed_amd import scoring, subset_index, synthetic
 from data_diet_distributed_amd.get_scores_and_prune import sparse_loader
 from data_diet_distributed_amd.loader import ArrayImageDataset, MyDataset
 from data_diet_distributed_amd.resnet import ResNet
@@ -124,9 +124,9 @@ def test_nn_is_bitwise_invariant(cuda, case, monkeypatch):
             saved.append(t.clone())
         return inner(t, lengths, group)
 
-    monkeypatch.setattr(scoring, "gather_rows", recording)
+    monkeypatch.setattr(forward_scores, "gather_rows", recording)
     one = engine(case, cuda, methods).score_shard(img, lab, 0, N)
-    monkeypatch.setattr(scoring, "gather_rows", inner)
+    monkeypatch.setattr(forward_scores, "gather_rows", inner)
     assert len(saved) == K
     for kw in ({"el2n_chunk": 256}, {"el2n_chunk": 1024}, {"lanes": 2},
                {"lanes": 2, "el2n_chunk": 256}):
@@ -147,9 +147,9 @@ def test_nn_is_bitwise_invariant(cuda, case, monkeypatch):
         bounds = [shard_bounds(N, 128, W, r) for r in range(W)]
         for r, (lo, hi) in enumerate(bounds):
             turn = iter(saved)
-            monkeypatch.setattr(scoring, "shard_lengths",
+            monkeypatch.setattr(forward_scores, "shard_lengths",
                                 lambda n, group=None: ([b - a for a, b in bounds], r))
-            monkeypatch.setattr(scoring, "gather_rows", lambda t, lengths, group=None: (
+            monkeypatch.setattr(forward_scores, "gather_rows", lambda t, lengths, group=None: (
                 lab if t.dim() == 1 else next(turn)))
             got = engine(case, cuda, ("el2n", "nn")).score_shard(img, lab, lo, hi)
             assert torch.equal(got["nn"], one["nn"][lo:hi]), (W, r)
@@ -243,6 +243,22 @@ def test_singleton_class_raises_by_name(cuda, case):
     lab[int(members[0])] = C  # ... and a label outside [0, C) is still a LabelError
     with pytest.raises(_capi.LabelError, match="1 label"):
         engine(case, cuda, ("nn",)).run(case["img"], lab, 0.5)
+
+
+@pytest.mark.parametrize("methods", [("nn",), ("proto", "nn"), ("loss", "proto", "nn"),
+                                     ("el2n", "loss"), ("grand", "nn"), ("nn", "grand")],
+                         ids=lambda m: "+".join(m))
+def test_each_bad_label_is_counted_once(cuda, case, methods):
+    """One label outside [0, C) among 130 rows (a full batch and a ragged 2) over K = 3
+    checkpoints is reported as one label, whichever kernel or class count does the counting:
+    not once per checkpoint, per pass or per requested score."""
+    lab = case["lab"].clone()
+    counts = torch.bincount(lab[:130], minlength=C)
+    row = int(torch.nonzero(lab[:130] == int(counts.argmax()))[0])
+    assert int(counts.max()) >= 3  # the class keeps at least two members: no singleton
+    lab[row] = C
+    with pytest.raises(_capi.LabelError, match="1 label"):
+        engine(case, cuda, methods).score_shard(case["img"], lab, 0, 130)
 
 
 def test_outer_layers(cuda, case, dup_case, tmp_path):
