@@ -47,6 +47,7 @@ EXPORTS = (
     "dd_logit_scores", "dd_variability_finalize",
     "dd_class_feature_sums", "dd_class_centroids", "dd_proto_scores",
     "dd_nn_workspace_bytes", "dd_nn_same_class",
+    "dd_knn_workspace_bytes", "dd_knn",
 )
 
 
@@ -101,6 +102,9 @@ def lib():
                 "dd_nn_workspace_bytes": (SZ, [I64, I64, I32, I32]),
                 "dd_nn_same_class": (I32, [P, P, P, I64, P, P, P, I64, I64, I32, I32, P, P, P,
                                            P, SZ, P]),
+                "dd_knn_workspace_bytes": (SZ, [I64, I64, I32, I32, I32, I32]),
+                "dd_knn": (I32, [P, P, P, I64, P, P, P, I64, I32, I32, I32, I32, P, P, P, P, P,
+                                 P, P, SZ, P]),
                 "dd_conv_pegrad_method": (I32, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_workspace_bytes": (SZ, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_sqnorm": (I32, [P, P, ctypes.POINTER(ConvGeom), P, I32, I32, P,
@@ -502,6 +506,78 @@ def nn_same_class(q: torch.Tensor, q_id: torch.Tensor, q_off: torch.Tensor, c: t
         nc, C, D, code, *ptrs, _dev(workspace, torch.uint8, "workspace"),
         workspace.numel() * workspace.element_size(), _stream(q))
     _check(rc, "dd_nn_same_class")
+    # the fp32 rows read twice (pack, value), the halves written once
+    _t1(e0, "el2n", (nq + nc) * (8.0 * D + 4.0 * Dp), q)
+    return workspace
+
+
+# ---- the k nearest neighbours over all classes -------------------------------------------------
+KNN_MAX_K = 16      # DD_KNN_MAX_K
+KNN_MAX_SPLITS = 64
+
+
+def knn_workspace_bytes(nq: int, nc: int, D: int, k: int, splits: int = 0,
+                        operands: str = "f16x3") -> int:
+    """Bytes of knn's workspace for the same `splits` (dd_knn_workspace_bytes; 0 for sizes outside
+    the entry point's limits)."""
+    return int(lib().dd_knn_workspace_bytes(int(nq), int(nc), int(D), int(k), int(splits),
+                                            OPERANDS[operands]))
+
+
+def knn(q: torch.Tensor, q_id: torch.Tensor, c: torch.Tensor, c_id: torch.Tensor, k: int, *,
+        q_label=None, c_label=None, splits: int = 0, operands: str = "f16x3", dist=None,
+        nbr_id=None, mean_dist=None, disagree=None, accum_dist=None, accum_disagree=None,
+        workspace=None):
+    """Per row of q [nq, D]: its k nearest rows of c [nc, D], any class, whose c_id differs from
+    the row's q_id, by (squared distance, id) (dd_knn).  Writes whichever are given of dist fp32
+    [nq, k] and nbr_id int64 [nq, k] (ascending), mean_dist fp32 [nq] (the mean of the k
+    distances), disagree fp32 [nq] (the share of the k whose c_label differs from the row's
+    q_label; both int64 label vectors are then required) and the accumulators accum_dist /
+    accum_disagree fp32 [nq] (+=).  With fewer than k candidates: +inf / -1 in the unused slots,
+    mean_dist +inf, disagree NaN; NaN / -1 for a non-finite query row.  splits: candidate segments
+    per query tile (0: chosen from nq and nc; no output depends on it).  workspace: a uint8
+    tensor of knn_workspace_bytes, or None to allocate one.  Returns the workspace."""
+    _dev(q, torch.float32, "q", 2)
+    _dev(c, torch.float32, "c", 2)
+    nq, D = q.shape
+    nc = c.shape[0]
+    if c.shape[1] != D:
+        raise ValueError(f"c must be [nc, {D}] (got {tuple(c.shape)})")
+    k, splits = int(k), int(splits)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"knn: k must be in 1..{KNN_MAX_K} (got {k})")
+    if not 0 <= splits <= KNN_MAX_SPLITS:
+        raise ValueError(f"knn: splits must be in 0..{KNN_MAX_SPLITS} (got {splits})")
+    outs = (dist, nbr_id, mean_dist, disagree, accum_dist, accum_disagree)
+    if all(o is None for o in outs):
+        raise ValueError("knn: no output requested")
+    labelled = disagree is not None or accum_disagree is not None
+    if labelled and (q_label is None or c_label is None):
+        raise ValueError("knn: disagree / accum_disagree need q_label and c_label")
+    code = _operands_code(operands)
+    need = int(lib().dd_knn_workspace_bytes(nq, nc, D, k, splits, code))
+    if need == 0:
+        raise ValueError(f"knn: unsupported size nq={nq}, nc={nc}, D={D}")
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ptrs = [_opt(dist, torch.float32, "dist", nq * k), _opt(nbr_id, torch.int64, "nbr_id", nq * k),
+            _opt(mean_dist, torch.float32, "mean_dist", nq),
+            _opt(disagree, torch.float32, "disagree", nq),
+            _opt(accum_dist, torch.float32, "accum_dist", nq),
+            _opt(accum_disagree, torch.float32, "accum_disagree", nq)]
+    labs = [_opt(q_label if labelled else None, torch.int64, "q_label", nq),
+            _opt(c_label if labelled and nc else None, torch.int64, "c_label", nc)]
+    if nq == 0:  # nothing to do (and an empty tensor's pointer is NULL: "not requested")
+        return workspace
+    Dp = (D + 15) // 16 * 16
+    e0 = _t0(q, always=True)
+    rc = lib().dd_knn(
+        _dev(q, torch.float32, "q"), _opt(q_id, torch.int64, "q_id", nq), labs[0], nq,
+        _opt(c if nc else None, torch.float32, "c"),
+        _opt(c_id if nc else None, torch.int64, "c_id", nc), labs[1], nc, D, k, splits, code,
+        *ptrs, _dev(workspace, torch.uint8, "workspace"),
+        workspace.numel() * workspace.element_size(), _stream(q))
+    _check(rc, "dd_knn")
     # the fp32 rows read twice (pack, value), the halves written once
     _t1(e0, "el2n", (nq + nc) * (8.0 * D + 4.0 * Dp), q)
     return workspace

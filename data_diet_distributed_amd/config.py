@@ -17,9 +17,12 @@ DEFAULTS = {
     # el2n and/or grand and/or the other logit scores of the EL2N forward: loss | margin |
     # entropy | error | wrong_mass | variability (scoring.LOGIT_METHODS) | proto (the distance
     # to the class prototype in feature space, scoring.FEATURE_METHODS) | nn (the distance to
-    # the nearest other example of the same class, scoring.NEIGHBOR_METHODS); select_by takes any
+    # the nearest other example of the same class, scoring.NEIGHBOR_METHODS) | knn, knn_disagree
+    # (the mean distance to the knn_k nearest other examples of any class and the share of them
+    # with another label, scoring.KNN_METHODS); select_by takes any
     "score_methods": ["el2n"],
     "select_by": "el2n",
+    "knn_k": 5,                       # neighbours of knn / knn_disagree (1..16)
     "select_policy": "global",        # global (reference) | stratified | balanced class quotas
     "select_skip": 0,                 # ranks skipped from the top before the k kept ones
     "score_checkpoints": 1,           # K (seed{k}/ckpt_{epoch}.pth when K > 1)

@@ -1,12 +1,14 @@
 """The consumers of the EL2N pass's train-BN forward: LogitScores (el2n + LOGIT_METHODS, from
-each launch's logits), ProtoScore and NNScore (from the checkpoint's pooled feature rows, over
-every rank), and ForwardScores, which holds the requested ones for one score_shard call.
+each launch's logits), ProtoScore, NNScore and KNNScore (from the checkpoint's pooled feature
+rows, over every rank), and ForwardScores, which holds the requested ones for one score_shard
+call.
 
 The pass hands every launch's logits to `consume` and, when `features` is not None, writes the
 launch's feature rows there; after a checkpoint's last chunk it calls `end_checkpoint`.  Every
 rank issues its collectives in the same order: the counts all-reduce (proto) and the lengths and
-labels all-gathers (nn) at construction, then per checkpoint the proto all-reduce followed by
-the nn all-gather.
+labels all-gathers (nn and the knn scores: one of each, shared, GatheredRows) at construction,
+then per checkpoint the proto all-reduce followed by the one all-gather of the feature rows that
+nn and the knn scores share.
 """
 from __future__ import annotations
 
@@ -16,7 +18,7 @@ import torch
 
 from . import _capi
 from .collectives import _all_reduce_sum, gather_rows, shard_lengths, world_of
-from .methods import LOGIT_FAMILY
+from .methods import KNN_METHODS, LOGIT_FAMILY
 
 
 def check_class_sizes(largest: int):
@@ -69,6 +71,31 @@ def nearest_same_class(features: torch.Tensor, labels: torch.Tensor, num_classes
     dist_sorted = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)
     _capi.nn_same_class(rows, order, off, rows, order, off, operands=operands, dist=dist_sorted)
     return torch.empty_like(dist_sorted).index_copy_(0, order, dist_sorted)
+
+
+def check_knn_size(N: int, k: int):
+    """Every row of the knn scores needs k other rows: reject a dataset of N <= k rows."""
+    if N <= k:
+        raise ValueError(f"knn_k={k} needs more than {k} examples in the whole dataset (got "
+                         f"{N}): a row would have fewer than knn_k neighbours (score +inf)")
+
+
+def nearest_k(features: torch.Tensor, labels: torch.Tensor, num_classes: int, k: int,
+              operands: str = "f16x3"):
+    """(knn fp32 [n], knn_disagree fp32 [n]): each row's mean distance to its k nearest other
+    rows of `features` [n, D], any class, and the share of them with another label (one dd_knn
+    launch; a tie goes to the smaller row index).  Raises LabelError for a label outside [0, C)
+    and ValueError for n <= k."""
+    labels = labels.contiguous()
+    _capi.class_counts(labels, num_classes, check=True)
+    n = features.shape[0]
+    check_knn_size(n, k)
+    ids = torch.arange(n, dtype=torch.int64, device=features.device)
+    mean = torch.empty(n, dtype=torch.float32, device=features.device)
+    share = torch.empty_like(mean)
+    _capi.knn(features, ids, features, ids, k, q_label=labels, c_label=labels, operands=operands,
+              mean_dist=mean, disagree=share)
+    return mean, share
 
 
 def ensemble_mean(acc: torch.Tensor, K: int) -> torch.Tensor:
@@ -164,43 +191,57 @@ class ProtoScore:
         return {"proto": ensemble_mean(self.accum, K)}
 
 
+class GatheredRows:
+    """The shard's place among every rank's rows, shared by nn and the knn scores: the shard
+    lengths and this rank's index (one all-gather), every rank's labels (one all-gather; labels
+    do not change across checkpoints; `labels` itself on one rank) and, per checkpoint, `gather`:
+    the one all-gather of the feature rows."""
+
+    def __init__(self, labels: torch.Tensor, group):
+        self.group = group
+        self.lengths, self.rank = shard_lengths(labels.numel(), group)
+        self.labels = gather_rows(labels, self.lengths, group)
+        self.local = self.labels is labels  # one rank: the candidates are the queries
+        self.offset = sum(self.lengths[:self.rank])
+
+    def gather(self, features: torch.Tensor) -> torch.Tensor:
+        return gather_rows(features, self.lengths, self.group)
+
+
 class NNScore:
     """The per-call state of the nn score for the shard's `labels` [n], built once and reused by
-    every checkpoint (labels do not change across checkpoints): every rank's labels (one
-    all-gather), the class offsets of the whole dataset and of this shard (dd_class_counts; `bad`
-    is this shard's count of labels outside [0, C)), the class-sorted order of the candidates (all
-    rows) and of the queries (this rank's rows) with their global ids, the class-ordered row
-    buffers, the class-ordered accumulator and the kernel's workspace (4 (n + N) pad16(D) bytes).
+    every checkpoint: from every rank's labels (`rows`) the class offsets of the whole dataset
+    and of this shard (dd_class_counts; `bad` is this shard's count of labels outside [0, C)),
+    the class-sorted order of the candidates (all rows) and of the queries (this rank's rows)
+    with their global ids, the class-ordered row buffers, the class-ordered accumulator and the
+    kernel's workspace (4 (n + N) pad16(D) bytes).
     The whole dataset's counts are read to the host once: a class of exactly one member is
     rejected by name."""
 
-    def __init__(self, labels: torch.Tensor, linear, group, operands: str):
+    def __init__(self, labels: torch.Tensor, linear, rows: GatheredRows, operands: str):
         n, dev = labels.numel(), labels.device
         C, D = linear.out_features, linear.in_features
         _check_width("nn", D)
-        self.group, self.operands = group, operands
-        labels = labels.contiguous()
-        self.lengths, rank = shard_lengths(n, group)
-        all_labels = gather_rows(labels, self.lengths, group)
+        self.operands = operands
+        all_labels = rows.labels
         self.q_order, self.q_off, counts, self.bad = class_grouping(labels, C)
-        if all_labels is labels:  # one rank: the candidates are the queries
+        if rows.local:  # one rank: the candidates are the queries
             self.c_order, self.c_off, self.c = self.q_order, self.q_off, None
         else:
             self.c_order, self.c_off, counts, _ = class_grouping(all_labels.contiguous(), C)
             self.c = torch.empty((all_labels.numel(), D), dtype=torch.float32, device=dev)
         check_no_singleton_class(counts.tolist())  # the one read of the counts
-        self.q_id = self.q_order + sum(self.lengths[:rank])
+        self.q_id = self.q_order + rows.offset
         self.q = torch.empty((n, D), dtype=torch.float32, device=dev)
         self.accum = torch.zeros(n, dtype=torch.float32, device=dev)
         need = _capi.nn_workspace_bytes(n, all_labels.numel(), D, operands)
         self.workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
 
-    def end_checkpoint(self, features: torch.Tensor):
-        """At the same point of a checkpoint as ProtoScore's: one all-gather of the feature rows
-        (world > 1), the rows gathered into class order, one dd_nn_same_class launch that
-        accumulates in class order."""
+    def end_checkpoint(self, features: torch.Tensor, allf: torch.Tensor):
+        """At the same point of a checkpoint as ProtoScore's, with every rank's feature rows
+        `allf` (GatheredRows.gather): the rows gathered into class order, one dd_nn_same_class
+        launch that accumulates in class order."""
         torch.index_select(features, 0, self.q_order, out=self.q)
-        allf = gather_rows(features, self.lengths, self.group)
         cand = self.q if self.c is None else torch.index_select(allf, 0, self.c_order,
                                                                 out=self.c)
         self.workspace = _capi.nn_same_class(
@@ -211,6 +252,43 @@ class NNScore:
         """The ensemble mean, scattered from class order back to shard order."""
         acc = torch.empty_like(self.accum).index_copy_(0, self.q_order, self.accum)
         return {"nn": ensemble_mean(acc, K)}
+
+
+class KNNScore:
+    """The per-call state of the knn scores (`methods`: those requested among KNN_METHODS) for the
+    shard's `labels` [n] and k neighbours, built once and reused by every checkpoint.  The
+    queries are the shard's rows in shard order with ids arange(n) + the shard's offset, the
+    candidates every rank's rows in dataset order with ids arange(N) and every rank's labels
+    (`rows`); `bad` is this shard's count of labels outside [0, C).  Holds the accumulators and
+    the kernel's workspace (4 (n + N) pad16(D) + 4 N + 8 n splits k bytes).  A dataset of
+    N <= k rows is rejected by name."""
+
+    def __init__(self, methods, labels: torch.Tensor, linear, rows: GatheredRows, operands: str,
+                 k: int):
+        n, dev = labels.numel(), labels.device
+        C, D = linear.out_features, linear.in_features
+        _check_width("knn", D)
+        N = sum(rows.lengths)
+        check_knn_size(N, k)
+        self.operands, self.k = operands, int(k)
+        _, self.bad = _capi.class_counts(labels, C, check=False)
+        self.q_id = torch.arange(n, dtype=torch.int64, device=dev) + rows.offset
+        self.c_id = self.q_id if rows.local else torch.arange(N, dtype=torch.int64, device=dev)
+        self.q_label, self.c_label = labels, rows.labels.contiguous()
+        self.acc = {m: torch.zeros(n, dtype=torch.float32, device=dev) for m in methods}
+        need = _capi.knn_workspace_bytes(n, N, D, self.k, 0, operands)
+        self.workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+
+    def end_checkpoint(self, features: torch.Tensor, allf: torch.Tensor):
+        """At the same point of a checkpoint as NNScore's, on the same gathered rows `allf`: one
+        dd_knn launch that accumulates the requested scores."""
+        self.workspace = _capi.knn(
+            features, self.q_id, allf, self.c_id, self.k, q_label=self.q_label,
+            c_label=self.c_label, operands=self.operands, accum_dist=self.acc.get("knn"),
+            accum_disagree=self.acc.get("knn_disagree"), workspace=self.workspace)
+
+    def finalize(self, K: int) -> Dict[str, torch.Tensor]:
+        return {m: ensemble_mean(a, K) for m, a in self.acc.items()}
 
 
 class ForwardScores:
@@ -227,15 +305,21 @@ class ForwardScores:
         n, methods = labels.numel(), cfg.methods
         logit = [m for m in methods if m in LOGIT_FAMILY]
         self.logit = LogitScores(logit, n, labels.device) if logit else None
-        self.proto = self.nn = None
+        self.proto = self.nn = self.knn = self.rows = None
         if "proto" in methods:
             self.proto = ProtoScore(labels, linear, group, cfg.batch_size)
+        knn = [m for m in methods if m in KNN_METHODS]
+        if "nn" in methods or knn:
+            labels = labels.contiguous()
+            self.rows = GatheredRows(labels, group)
         if "nn" in methods:
-            self.nn = NNScore(labels, linear, group, cfg.el2n_operands)
+            self.nn = NNScore(labels, linear, self.rows, cfg.el2n_operands)
+        if knn:
+            self.knn = KNNScore(knn, labels, linear, self.rows, cfg.el2n_operands, cfg.knn_k)
         # the one [n, D] fp32 buffer of the checkpoint's feature rows (n D 4 bytes: 102 MB at
         # 50 000 x 512, 10.5 GB for 1.28 M x 2048 rows on one rank), or None: logits only
         self.features = None
-        by_features = self.proto or self.nn
+        by_features = self.proto or self.nn or self.knn
         if by_features:
             self.features = torch.empty((n, linear.in_features), dtype=torch.float32,
                                         device=labels.device)
@@ -255,11 +339,15 @@ class ForwardScores:
         ordered after it."""
         if self.proto is not None:
             self.proto.end_checkpoint(self.features)
-        if self.nn is not None:
-            self.nn.end_checkpoint(self.features)
+        if self.rows is not None:  # one all-gather of the rows serves nn and the knn scores
+            allf = self.rows.gather(self.features)
+            if self.nn is not None:
+                self.nn.end_checkpoint(self.features, allf)
+            if self.knn is not None:
+                self.knn.end_checkpoint(self.features, allf)
 
     def _parts(self):
-        return [p for p in (self.logit, self.proto, self.nn) if p is not None]
+        return [p for p in (self.logit, self.proto, self.nn, self.knn) if p is not None]
 
     def tensors(self) -> List[torch.Tensor]:
         """Every device buffer the pass and the second phase touch (for the streams'

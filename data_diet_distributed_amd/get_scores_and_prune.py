@@ -43,6 +43,19 @@ from .subset_index import write_subset_index
 from .synthetic import state_digest
 
 
+FEATURE_SCORES = ("nn", "knn", "knn_disagree")  # from the rows the classifier consumes
+
+
+def _feature_scores(feats, labels, num_classes, score, knn_k):
+    """The chosen score of FEATURE_SCORES among the visited rows `feats` [n, D] (LabelError for
+    a label outside [0, C))."""
+    from .forward_scores import nearest_k, nearest_same_class
+    if score == "nn":
+        return nearest_same_class(feats, labels, num_classes)
+    mean, share = nearest_k(feats, labels, num_classes, knn_k)
+    return mean if score == "knn" else share
+
+
 def _score_rows(logits, labels, out, bad, score="el2n"):
     """out[b] = the chosen score of each row of one launch's logits: EL2N (dd_el2n), or one of
     the single-forward logit statistics (dd_logit_scores accumulating into zeros)."""
@@ -54,10 +67,12 @@ def _score_rows(logits, labels, out, bad, score="el2n"):
 
 
 def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect=None,
-                            score="el2n"):
+                            score="el2n", knn_k=5):
     """Scores of every example the loader yields, in visit order, plus the visited indices
     (`score`: "el2n" or one of _capi.LOGIT_STATS, from the same logits; or "nn", the distance to
-    the nearest visited example of the same class, from the rows `net.linear` consumes).
+    the nearest visited example of the same class, or "knn" / "knn_disagree", the mean distance
+    to the knn_k nearest visited examples and the share of them with another label, from the rows
+    `net.linear` consumes).
     A dict given as `collect` receives "labels" (the targets in visit order, int64 on the
     device) and "num_classes" (the width of the logits), for the class selection policies.
 
@@ -68,10 +83,10 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
     bad = _capi.label_counter(device)
     C = None
     feats, hook = [], None
-    if score == "nn":  # the classifier's input rows of the same forward
+    if score in FEATURE_SCORES:  # the classifier's input rows of the same forward
         head = getattr(net.module if hasattr(net, "module") else net, "linear", None)
         if not isinstance(head, torch.nn.Linear):
-            raise ValueError("score='nn' needs a net whose classifier is `net.linear`")
+            raise ValueError(f"score={score!r} needs a net whose classifier is `net.linear`")
         hook = head.register_forward_pre_hook(
             lambda _m, args: feats.append(args[0].detach().float().flatten(1)))
     try:
@@ -95,8 +110,8 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
         if hook is not None:
             hook.remove()
     if hook is not None and visit:
-        from .forward_scores import nearest_same_class
-        scores = [nearest_same_class(torch.cat(feats).contiguous(), torch.cat(targets), C)]
+        scores = [_feature_scores(torch.cat(feats).contiguous(), torch.cat(targets), C, score,
+                                  knn_k)]
     if collect is not None:
         collect["labels"] = (torch.cat(targets) if targets
                              else torch.empty(0, dtype=torch.int64, device=device))
@@ -297,7 +312,8 @@ def fast_path(train_loader, net, device):
     return src, model
 
 
-def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, score="el2n"):
+def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, score="el2n",
+                     knn_k=5):
     """Scores in visit order + visited indices, like el2n_scores_from_loader, on the hand
     kernels: every visit batch of the loader's BatchSampler (all of size B but a ragged last
     one) is one BN group; chunks of whole batches are gathered + normalised on device."""
@@ -325,7 +341,7 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
     scores = torch.empty(n, dtype=torch.float32, device=dev)
     bad = _capi.label_counter(dev)
     feats = (torch.empty((n, model.linear.in_features), dtype=torch.float32, device=dev)
-             if score == "nn" else None)
+             if score in FEATURE_SCORES else None)
     with torch.inference_mode():
         for c0 in range(0, n, CH):
             c1 = min(n, c0 + CH)
@@ -341,8 +357,8 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
             logits = el2n_fast.forward_logits(model, xb, B, rows)[:rows]
             _score_rows(logits.contiguous(), lab_d[idx], scores[c0:c1], bad, score)
         if feats is not None:  # neighbours among the visited examples (LabelError inside)
-            from .forward_scores import nearest_same_class
-            return nearest_same_class(feats, lab_d[visit_d], model.linear.out_features), visit_d
+            return _feature_scores(feats, lab_d[visit_d], model.linear.out_features, score,
+                                   knn_k), visit_d
     # a label outside [0, C): the reference's one_hot raises (:17), so does this path
     _capi.check_labels(bad, model.linear.out_features, "sparse_loader")
     return scores, visit_d
@@ -392,7 +408,8 @@ def refine_fast_keep_set(train_loader, src, model, device, scores, visit, sample
 
 def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size, num_workers,
                   *, dataset=None, subset_index_path=None, return_indices=False,
-                  fast: bool = True, refine="auto", policy="global", skip=0, score="el2n"):
+                  fast: bool = True, refine="auto", policy="global", skip=0, score="el2n",
+                  knn_k=5):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
@@ -411,6 +428,9 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     "nn" ranks by the distance to the nearest visited example of the same class in feature space
     (the rows the classifier consumes, from the same single forward; dd_nn_same_class), so the
     default policy drops near-duplicates first; a class with exactly one visited member raises.
+    "knn" ranks by the mean distance to the knn_k nearest visited examples of any class and
+    "knn_disagree" by the share of those neighbours that carry another label (dd_knn on the same
+    rows; knn_k in 1.._capi.KNN_MAX_K, fewer visited examples than knn_k + 1 raise).
     "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
     over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
     score="el2n"."""
@@ -420,9 +440,13 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     if score in ("variability", "grand", "proto"):
         raise ValueError(f"score={score!r} is computed by the scoring engine "
                          f"(scoring.ScoringEngine / score.py), not by sparse_loader")
-    if score not in ("el2n", "nn") and score not in _capi.LOGIT_STATS:
-        raise ValueError(f"score must be 'el2n', 'nn' or one of {_capi.LOGIT_STATS} "
-                         f"(got {score!r})")
+    if score != "el2n" and score not in FEATURE_SCORES + _capi.LOGIT_STATS:
+        raise ValueError(f"score must be 'el2n', one of {FEATURE_SCORES} or one of "
+                         f"{_capi.LOGIT_STATS} (got {score!r})")
+    if score in ("knn", "knn_disagree") and (
+            isinstance(knn_k, bool) or not isinstance(knn_k, (int, np.integer))
+            or not 1 <= knn_k <= _capi.KNN_MAX_K):
+        raise ValueError(f"knn_k must be an integer in 1..{_capi.KNN_MAX_K} (got {knn_k!r})")
     if refine is True and score != "el2n":
         raise ValueError("refine=True re-scores EL2N only: it needs score='el2n'")
     skip = check_selection(policy, skip, "policy", "skip")
@@ -438,11 +462,12 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     fp = fast_path(train_loader, net, device) if fast else None
     sparse_loader.last_path = "fast" if fp is not None else "general"
     if fp is not None:
-        scores, visit = el2n_scores_fast(train_loader, fp[0], fp[1], device, score=score)
+        scores, visit = el2n_scores_fast(train_loader, fp[0], fp[1], device, score=score,
+                                         knn_k=knn_k)
     else:
         seen = None if policy == "global" else {}  # a class policy needs the visited targets
         scores, visit = el2n_scores_from_loader(train_loader, net, device, collect=seen,
-                                                score=score)
+                                                score=score, knn_k=knn_k)
     samples = _capi.keep_count(train_samples, sparsity)
     if samples < 0 or samples > scores.numel():
         raise ValueError(f"keep count {samples} outside [0, {scores.numel()}]")
@@ -481,6 +506,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                             "bn_mode": "train" if module.training else "eval",
                             "order": "loader visit order (reference semantics)",
                             "checkpoint_digests": [digest],
+                            **({"knn_k": int(knn_k)} if score in ("knn", "knn_disagree") else {}),
                             **({} if default_rule else {
                                 "select_policy": policy, "select_skip": int(skip),
                                 "class_quota": sparse_loader.last_selection["class_quota"],

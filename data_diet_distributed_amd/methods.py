@@ -26,16 +26,25 @@ FORWARD_FAMILY = LOGIT_FAMILY + FEATURE_METHODS
 NEIGHBOR_METHODS = ("nn",)
 # every score that comes from the EL2N forward
 FORWARD_SCORES = FORWARD_FAMILY + NEIGHBOR_METHODS
+# Scores of a row against its k nearest other rows of ANY class (k = ScoreConfig.knn_k), from
+# the same feature rows, the neighbourhood taken by (squared distance, example index):
+#   knn_i          = the mean of || f_i - f_j ||_2 over the k neighbours j (the density / coverage
+#                    measure of the coreset family; needs no labels)
+#   knn_disagree_i = the share of the k neighbours with y_j != y_i (deep k-NN filtering: a
+#                    mislabelled example sits among another class's rows)
+# Larger = more isolated / more suspicious.  They come from the EL2N forward too; FORWARD_SCORES
+# keeps its value and every decision goes through known() / pass_of().
+KNN_METHODS = ("knn", "knn_disagree")
 
 
 def known(method: str) -> bool:
-    return method == "grand" or method in FORWARD_SCORES
+    return method == "grand" or method in FORWARD_SCORES or method in KNN_METHODS
 
 
 def pass_of(method: str) -> str:
-    """The pass that computes `method`: "el2n" (the shared forward of the logit family and the
-    feature scores) or "grand"."""
-    return "el2n" if method in FORWARD_SCORES else "grand"
+    """The pass that computes `method`: "el2n" (the shared forward of the logit family, the
+    feature scores and the neighbour scores) or "grand"."""
+    return "el2n" if method in FORWARD_SCORES or method in KNN_METHODS else "grand"
 
 
 def refinable(method: str) -> bool:

@@ -137,6 +137,7 @@ def engine_config(cfg):
                        refine_max_frac=float(cfg.get("refine_max_frac", 0.08)),
                        select_policy=str(cfg.get("select_policy", "global")),
                        select_skip=int(cfg.get("select_skip", 0)),
+                       knn_k=int(cfg.get("knn_k", 5)),
                        **SCORE_PRECISIONS[prec])
 
 
@@ -184,6 +185,8 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
                 "grand_batch": ecfg.grand_batch, "world_size": world,
                 "order": "score descending, ties by ascending index (pinned batch partition)",
                 "seconds": secs, "examples_per_s": n / secs if secs > 0 else None}
+        if any(m in ("knn", "knn_disagree") for m in ecfg.methods):
+            meta["knn_k"] = int(ecfg.knn_k)  # (a run without them: metadata unchanged)
         sel = eng.last_selection
         if sel["policy"] != "global" or sel["skip"]:  # (a default run's metadata is unchanged)
             meta.update(select_policy=sel["policy"], select_skip=sel["skip"],

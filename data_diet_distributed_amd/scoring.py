@@ -15,7 +15,9 @@ device-resident pipeline:
               (dd_class_feature_sums -> one int64 all-reduce -> dd_class_centroids ->
               dd_proto_scores); "nn" takes, from those same rows, the distance to the nearest
               other row of the same class over all ranks (one all-gather of the rows ->
-              dd_nn_same_class: an all-pairs search per class on split MFMA)
+              dd_nn_same_class: an all-pairs search per class on split MFMA); "knn" and
+              "knn_disagree" take the knn_k nearest other rows of any class from the same
+              gathered rows (dd_knn): their mean distance and the share with another label
       GraNd : eval-BN forward with a tape of Conv2d/Linear (input, output) -> dd_el2n emits the
               residual e = d(sum CE)/d(logits) -> autograd back to every conv output only
               (weights frozen: no weight-gradient GEMMs) -> dd_conv_pegrad_sqnorm per conv
@@ -47,8 +49,8 @@ from .collectives import (_all_reduce_sum, _world, all_shards, gather_padded,  #
 from .forward_scores import (ForwardScores, check_class_sizes,  # noqa: F401
                              check_no_singleton_class, ensemble_mean, nearest_same_class)
 from .methods import (FEATURE_METHODS, FORWARD_FAMILY, FORWARD_SCORES,  # noqa: F401
-                      LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS, SELECT_POLICIES,
-                      check_selection, known, pass_of, refinable)
+                      KNN_METHODS, LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS,
+                      SELECT_POLICIES, check_selection, known, pass_of, refinable)
 from .resnet import ResNet
 
 MEAN = (0.4914, 0.4822, 0.4465)  # reference data/loader.py:10
@@ -62,8 +64,11 @@ class ScoreConfig:
     # family shares one forward per checkpoint) + FEATURE_METHODS ("proto": the distance of the
     # pooled feature row to its class's mean over the whole dataset, from that same forward)
     # + NEIGHBOR_METHODS ("nn": the distance to the nearest other row of the same class)
+    # + KNN_METHODS ("knn", "knn_disagree": the mean distance to the knn_k nearest other rows of
+    # any class, and the share of them that carry another label)
     methods: Sequence[str] = ("el2n",)
     select_by: str = "el2n"                  # which ensemble score ranks the keep-set
+    knn_k: int = 5                           # neighbours of the KNN_METHODS (1.._capi.KNN_MAX_K)
     batch_size: int = 128                    # EL2N batch partition (config.yaml:7 batch_size)
     el2n_bn: str = "batch"                   # "batch" = reference semantics; "running" = eval
     grand_batch: int = 1024                  # GraNd chunk (eval BN: any size, same result)
@@ -141,6 +146,11 @@ class ScoreConfig:
                 raise ValueError(f"unknown score method {m!r}")
         if self.select_by not in self.methods:
             raise ValueError(f"select_by={self.select_by!r} not among methods {self.methods}")
+        if any(m in KNN_METHODS for m in self.methods) and (
+                isinstance(self.knn_k, bool) or not isinstance(self.knn_k, (int, np.integer))
+                or not 1 <= self.knn_k <= _capi.KNN_MAX_K):
+            raise ValueError(f"knn_k must be an integer in 1..{_capi.KNN_MAX_K} "
+                             f"(got {self.knn_k!r})")
         if self.el2n_bn not in ("batch", "running"):
             raise ValueError("el2n_bn must be 'batch' or 'running'")
         if self.pegrad_method not in _capi.METHODS:
@@ -711,10 +721,10 @@ class ScoringEngine:
         range).  run() passes check=False and checks the gathered vectors instead (_validate),
         so that on W > 1 ranks every rank raises (or falls back) together.
 
-        "proto" and "nn" are the scores for which a shard is not a slice of the whole: the class
-        prototypes are means over every rank's rows, and a row's nearest neighbour may lie on
-        another rank.  run() passes its process `group`, over which forward_scores issues their
-        collectives; a direct call without a group takes both over [lo, hi) only."""
+        "proto", "nn" and the knn scores are those for which a shard is not a slice of the whole:
+        the class prototypes are means over every rank's rows, and a row's nearest neighbours
+        may lie on another rank.  run() passes its process `group`, over which forward_scores
+        issues their collectives; a direct call without a group takes them over [lo, hi) only."""
         n = hi - lo
         K = len(self.models)
         cfg = self.cfg

@@ -699,6 +699,66 @@ int dd_nn_same_class(const float* q, const int64_t* q_id, const int64_t* q_off, 
                      int64_t C, int32_t D, int32_t operands, float* dist, int64_t* nn_id,
                      float* accum, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * The k nearest neighbours of a row over ALL classes in feature space: the mean distance to them
+ * (a density / coverage signal that needs no labels) and the share of them that carry another
+ * label (deep k-NN label-noise filtering).  Purely additive: dd_abi_version() stays 10.
+ *
+ *   N_k(r) = the k candidates j with c_id[j] != q_id[r] with the smallest (d^2(r, j), c_id[j]),
+ *            compared lexicographically
+ *   mean_dist[r] = (1 / k) sum over j in N_k(r) of || q_r - c_j ||_2
+ *   disagree[r]  = |{ j in N_k(r) : c_label[j] != q_label[r] }| / k
+ *
+ * q fp32 [nq][D] (queries) and c fp32 [nc][D] (candidates), in any order; q_id / c_id int64: the
+ * rows' global example indices (distinct among the candidates); q_label / c_label int64, compared
+ * for equality only, and NULL is allowed when neither disagree nor accum_disagree is asked for.
+ *
+ * The search picks on dd_nn_same_class's key, key(r, j) = ||c_j||^2 - 2 q_r . c_j, the dot product
+ * on split MFMA (hi.hi + hi.lo + lo.hi of the `operands` halves, fp32 accumulation, 32x32x16, D
+ * zero-padded to a multiple of 16, K order fixed by D), and keeps the k smallest (key, c_id)
+ * pairs; a tie goes to the smaller id.  A workgroup searches one of `splits` contiguous candidate
+ * segments for 128 queries and writes the segment's k smallest pairs per query to the workspace;
+ * a second kernel takes the k smallest of those.  splits == 0 lets the library choose the count
+ * from nq and nc alone (two workgroups per compute unit where the sizes allow).  No atomics.  A
+ * candidate with a non-finite element is never picked (its key is NaN; only a finite key is
+ * admitted, so a pair whose halves leave the operand type's range, |v| >= 65504 in fp16, is not
+ * picked either).  The values are then taken in fp32 from the fp32 rows, one row per wave in an
+ * order fixed by D (dd_proto_scores' reduction), for slot i = 0 .. k - 1 in ascending (key, id):
+ *   dist[r][i] = sqrt(sum_d (q[r][d] - c[pick_i][d])^2),  nbr_id[r][i] = c_id[pick_i]
+ * so an exact duplicate contributes exactly 0 and the MFMA rounding decides only WHICH rows are
+ * picked: for every pick p, d^2(p) - d^2(k-th best) <= 2 eps (||q||^2 + max_j ||c_j||^2), eps as
+ * for dd_nn_same_class.  mean_dist is the sum of the k distances in slot order (accumulated in
+ * double, rounded once) over k; accum_dist[r] += mean_dist[r], accum_disagree[r] += disagree[r].
+ * Fewer than k admissible candidates: the unused slots hold dist = +inf and nbr_id = -1,
+ * mean_dist = +inf and disagree = NaN.  A query row with a non-finite element: NaN everywhere,
+ * ids of -1.  Any output may be NULL, not all.
+ *
+ * Invariance: a key is a function of the two rows and D alone, and the k smallest of a set of
+ * (key, id) pairs under one total order do not depend on how the set is split or traversed.  So
+ * every output of row r depends on row r, on the candidate SET, on D and on k: bitwise
+ * independent of `splits`, of the batching of the queries, of nq, of the rows' positions and the
+ * buffers' alignment, and of the launch geometry.
+ *
+ * Limits: 1 <= k <= DD_KNN_MAX_K, 1 <= D <= 4096, 0 <= nq, nc < 2^31, 0 <= splits <= 64, operands
+ * DD_OPERANDS_F16X3 or DD_OPERANDS_BF16X3; outside them, a NULL buffer the call would touch, no
+ * output requested, or a workspace that is too small or not 16-byte aligned is DD_EINVAL with a
+ * message before any launch.  nq == 0 returns DD_OK.  The workspace (dd_knn_workspace_bytes: host
+ * only, 0 for bad arguments; it depends on `splits` as passed to dd_knn) holds the halves of
+ * every row, split once per call, 4 (nq + nc) pad16(D) bytes, 4 nc bytes of norms and the
+ * partial lists, 8 nq splits k bytes, each region rounded up to 256.  No allocation, no
+ * synchronisation inside (graph-capturable); plain vector stores only.
+ * ---------------------------------------------------------------------------------------- */
+#define DD_KNN_MAX_K 16
+
+size_t dd_knn_workspace_bytes(int64_t nq, int64_t nc, int32_t D, int32_t k, int32_t splits,
+                              int32_t operands);
+
+int dd_knn(const float* q, const int64_t* q_id, const int64_t* q_label, int64_t nq,
+           const float* c, const int64_t* c_id, const int64_t* c_label, int64_t nc, int32_t D,
+           int32_t k, int32_t splits, int32_t operands, float* dist, int64_t* nbr_id,
+           float* mean_dist, float* disagree, float* accum_dist, float* accum_disagree,
+           void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
