@@ -8,6 +8,7 @@ consistent pointers and sizes.
 from __future__ import annotations
 
 import ctypes
+import itertools
 import math
 import os
 import threading
@@ -48,6 +49,7 @@ EXPORTS = (
     "dd_class_feature_sums", "dd_class_centroids", "dd_proto_scores",
     "dd_nn_workspace_bytes", "dd_nn_same_class",
     "dd_knn_workspace_bytes", "dd_knn",
+    "dd_kcenter_workspace_bytes", "dd_kcenter_seed_batch", "dd_kcenter_greedy",
 )
 
 
@@ -105,6 +107,10 @@ def lib():
                 "dd_knn_workspace_bytes": (SZ, [I64, I64, I32, I32, I32, I32]),
                 "dd_knn": (I32, [P, P, P, I64, P, P, P, I64, I32, I32, I32, I32, P, P, P, P, P,
                                  P, P, SZ, P]),
+                "dd_kcenter_workspace_bytes": (SZ, [I64, I32, I32, I64]),
+                "dd_kcenter_seed_batch": (I32, [I32, I32]),
+                "dd_kcenter_greedy": (I32, [P, P, I64, I32, P, I32, P, P, I64, P, I64, I32, I32,
+                                            P, P, P, P, P, SZ, P]),
                 "dd_conv_pegrad_method": (I32, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_workspace_bytes": (SZ, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_sqnorm": (I32, [P, P, ctypes.POINTER(ConvGeom), P, I32, I32, P,
@@ -581,6 +587,139 @@ def knn(q: torch.Tensor, q_id: torch.Tensor, c: torch.Tensor, c_id: torch.Tensor
     # the fp32 rows read twice (pack, value), the halves written once
     _t1(e0, "el2n", (nq + nc) * (8.0 * D + 4.0 * Dp), q)
     return workspace
+
+
+# ---- greedy k-center over feature rows (the coverage keep-set) ---------------------------------
+KCENTER_MAX_SEED_BATCH = 64    # DD_KCENTER_MAX_SEED_BATCH (tests/test_kcenter_select.py compares
+KCENTER_MAX_BLOCKS = 4096      # DD_KCENTER_MAX_BLOCKS       these three with the header's)
+KCENTER_MAX_GROUPS = 65535     # DD_KCENTER_MAX_GROUPS
+KCENTER_ID_LIMIT = 1 << 31     # example ids fit 31 bits
+
+
+def kcenter_workspace_bytes(n: int, D: int, G: int, steps: int) -> int:
+    """Bytes of kcenter_greedy's workspace (dd_kcenter_workspace_bytes; 0 for sizes outside the
+    entry point's limits)."""
+    return int(lib().dd_kcenter_workspace_bytes(int(n), int(D), int(G), int(steps)))
+
+
+def kcenter_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor, seed_counts,
+                   picks, *, seed_batch: int = 0, blocks: int = 0, check: bool = True):
+    """Farthest-first traversal inside groups (dd_kcenter_greedy).  rows fp32 [n, D] in ANY order;
+    ids int64 [n], the rows' example ids (distinct, in [0, 2^31); None: arange(n)); groups int64
+    [n], each row's group in [0, G) (None: one group; a row outside [0, G) is in no group);
+    sizes: host ints [G], the members per group; seeds: int64 device tensor, INDICES into `rows`
+    of the centres every group starts from, in any order, seed_counts[g] (host ints) of them in
+    group g; picks: host ints [G], the rows group g takes after its seeds (the host loop runs
+    max(picks) + 1 launches).  The rows are sorted into group order, ascending id inside a group,
+    here.
+
+    Returns (picked int64 [steps, G], radius2 fp32 [steps, G], mind2 fp32 [n], stat int32 [2]):
+    picked[t, g] is the id group g takes at step t and radius2[t, g] its squared distance to the
+    nearest kept row of its group at that moment (both -1 for t >= picks[g]); mind2, in the order
+    of `rows`, is every row's final squared distance to its nearest kept row (-1: kept; +inf: a
+    group that keeps nothing); stat = (rows with a non-finite element, ids outside [0, 2^31)).
+    With check the two counts are read back (one sync) and either raises ValueError; check=False
+    leaves them to the caller.  seed_batch / blocks: centres per seed launch and workgroups per
+    group (0: chosen by the library); no output depends on either."""
+    _dev(rows, torch.float32, "rows", 2)
+    n, D = rows.shape
+    dev = rows.device
+    sizes, seed_counts, picks = ([int(v) for v in x] for x in (sizes, seed_counts, picks))
+    G = len(sizes)
+    if not 1 <= G <= KCENTER_MAX_GROUPS:
+        raise ValueError(f"kcenter_greedy: need 1 <= G <= {KCENTER_MAX_GROUPS} (got {G})")
+    if len(seed_counts) != G or len(picks) != G:
+        raise ValueError("kcenter_greedy: sizes, seed_counts and picks need one entry per group")
+    if any(v < 0 for v in sizes + seed_counts + picks) or sum(sizes) > n:
+        raise ValueError("kcenter_greedy: negative count, or more group members than rows")
+    for g in range(G):
+        if seed_counts[g] + picks[g] > sizes[g]:
+            raise ValueError(f"kcenter_greedy: group {g} of {sizes[g]} rows cannot keep "
+                             f"{seed_counts[g]} seeds + {picks[g]} picks")
+        if picks[g] and not seed_counts[g]:
+            raise ValueError(f"kcenter_greedy: group {g} has picks but no seed")
+    _dev(seeds, torch.int64, "seeds", 1)
+    if seeds.numel() != sum(seed_counts):
+        raise ValueError(f"kcenter_greedy: {seeds.numel()} seeds, seed_counts sum to "
+                         f"{sum(seed_counts)}")
+    if groups is None and G != 1:
+        raise ValueError("kcenter_greedy: G > 1 needs `groups`")
+    seed_batch, blocks = int(seed_batch), int(blocks)
+    if not 0 <= seed_batch <= KCENTER_MAX_SEED_BATCH:
+        raise ValueError(f"kcenter_greedy: seed_batch must be in 0..{KCENTER_MAX_SEED_BATCH}")
+    if not 0 <= blocks <= KCENTER_MAX_BLOCKS:
+        raise ValueError(f"kcenter_greedy: blocks must be in 0..{KCENTER_MAX_BLOCKS}")
+    steps = max(picks)
+    need = int(lib().dd_kcenter_workspace_bytes(n, D, G, steps))
+    if need == 0:
+        raise ValueError(f"kcenter_greedy: unsupported size n={n}, D={D}, G={G}")
+    stat = torch.zeros(2, dtype=torch.int32, device=dev)
+    picked = torch.full((steps, G), -1, dtype=torch.int64, device=dev)
+    radius2 = torch.full((steps, G), -1.0, dtype=torch.float32, device=dev)
+    mind2 = torch.full((n,), float("inf"), dtype=torch.float32, device=dev)
+    if n:
+        # group order, ascending id inside a group (two stable sorts; none where the rows
+        # already are: one group, ids ascending by construction)
+        order = None
+        if ids is not None:
+            _dev(ids, torch.int64, "ids", 1)
+            if ids.numel() != n:
+                raise ValueError("ids must have one entry per row")
+            stat[1:2] = ((ids < 0) | (ids >= KCENTER_ID_LIMIT)).sum().to(torch.int32)
+            order = torch.argsort(ids, stable=True)
+        else:
+            ids = torch.arange(n, dtype=torch.int64, device=dev)
+        if groups is not None:
+            _dev(groups, torch.int64, "groups", 1)
+            if groups.numel() != n:
+                raise ValueError("groups must have one entry per row")
+            key = torch.where((groups >= 0) & (groups < G), groups, torch.full_like(groups, G))
+            if order is None:
+                order = torch.argsort(key, stable=True)
+            else:
+                order = order[torch.argsort(key[order], stable=True)]
+        pos = seeds
+        if order is not None:
+            rows, ids = rows.index_select(0, order), ids.index_select(0, order)
+            inv = torch.empty_like(order)
+            inv[order] = torch.arange(n, dtype=torch.int64, device=dev)
+            pos = inv[seeds]
+        pos = torch.sort(pos)[0].contiguous()  # group order: a group's seeds are contiguous
+        off, seed_off = (torch.tensor([0] + list(itertools.accumulate(v)),
+                                      dtype=torch.int64).to(dev) for v in (sizes, seed_counts))
+        picks_d = torch.tensor(picks, dtype=torch.int64).to(dev)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        mind2_s = mind2 if order is None else torch.empty_like(mind2)
+        e0 = _t0(rows, always=True)
+        rc = lib().dd_kcenter_greedy(
+            _dev(rows, torch.float32, "rows"), _dev(ids, torch.int64, "ids"), n, D,
+            _dev(off, torch.int64, "off"), G, _opt(pos if pos.numel() else None, torch.int64,
+                                                   "seeds"),
+            _dev(seed_off, torch.int64, "seed_off"), max(seed_counts),
+            _dev(picks_d, torch.int64, "picks"), steps, seed_batch, blocks,
+            _opt(picked if steps else None, torch.int64, "picked"),
+            _opt(radius2 if steps else None, torch.float32, "radius2"),
+            _dev(mind2_s, torch.float32, "mind2"), ctypes.c_void_p(stat.data_ptr()),
+            _dev(ws, torch.uint8, "workspace"), need, _stream(rows))
+        _check(rc, "dd_kcenter_greedy")
+        # every seed and pick launch streams the rows once (fewer as rows are kept)
+        per_launch = int(lib().dd_kcenter_seed_batch(D, seed_batch))
+        _t1(e0, "select", 4.0 * n * D * (steps + 1 + -(-max(seed_counts) // per_launch)), rows)
+        if order is not None:
+            mind2[order] = mind2_s
+    if check:
+        check_kcenter(stat.tolist())
+    return picked, radius2, mind2, stat
+
+
+def check_kcenter(stat):
+    """Raise ValueError on kcenter_greedy's counts (host ints): non-finite rows, ids past 31 bits."""
+    bad_rows, bad_ids = (int(v) for v in stat)
+    if bad_ids:
+        raise ValueError(f"kcenter: {bad_ids} example id(s) outside [0, 2^31)")
+    if bad_rows:
+        raise ValueError(f"kcenter: {bad_rows} feature row(s) with a NaN or infinite element: the "
+                         f"coverage keep-set is undefined")
 
 
 def label_counter(device) -> torch.Tensor:

@@ -25,6 +25,9 @@ DEFAULTS = {
     "knn_k": 5,                       # neighbours of knn / knn_disagree (1..16)
     "select_policy": "global",        # global (reference) | stratified | balanced class quotas
     "select_skip": 0,                 # ranks skipped from the top before the k kept ones
+    "select_fill": "score",           # score (the rank cut) | kcenter (coverage: greedy k-center)
+    "kcenter_seed_frac": 0.0,         # share of a quota seeded by the score (at least one seed)
+    "kcenter_ckpt": -1,               # the checkpoint whose feature rows span the space
     "score_checkpoints": 1,           # K (seed{k}/ckpt_{epoch}.pth when K > 1)
     "score_epoch": 19,
     "bn_mode": "batch",               # EL2N BN: batch (reference) | running (eval)

@@ -301,15 +301,18 @@ class ForwardScores:
     `bad` of the shard's labels here."""
 
     def __init__(self, cfg, labels: torch.Tensor, linear, group=None,
-                 counter: Optional[torch.Tensor] = None):
+                 counter: Optional[torch.Tensor] = None, kcenter_ckpt: Optional[int] = None):
         n, methods = labels.numel(), cfg.methods
+        # the kcenter fill (ScoreConfig.select_fill): every rank's feature rows of checkpoint
+        # `kcenter_ckpt` (0-based) are kept for run()'s selection
+        self.kcenter_ckpt, self.kcenter_rows, self._ckpts_done = kcenter_ckpt, None, 0
         logit = [m for m in methods if m in LOGIT_FAMILY]
         self.logit = LogitScores(logit, n, labels.device) if logit else None
         self.proto = self.nn = self.knn = self.rows = None
         if "proto" in methods:
             self.proto = ProtoScore(labels, linear, group, cfg.batch_size)
         knn = [m for m in methods if m in KNN_METHODS]
-        if "nn" in methods or knn:
+        if "nn" in methods or knn or kcenter_ckpt is not None:
             labels = labels.contiguous()
             self.rows = GatheredRows(labels, group)
         if "nn" in methods:
@@ -320,7 +323,9 @@ class ForwardScores:
         # 50 000 x 512, 10.5 GB for 1.28 M x 2048 rows on one rank), or None: logits only
         self.features = None
         by_features = self.proto or self.nn or self.knn
-        if by_features:
+        if kcenter_ckpt is not None:
+            _check_width("kcenter", linear.in_features)
+        if by_features or kcenter_ckpt is not None:
             self.features = torch.empty((n, linear.in_features), dtype=torch.float32,
                                         device=labels.device)
         self._counter = counter if self.logit is not None else None
@@ -339,12 +344,20 @@ class ForwardScores:
         ordered after it."""
         if self.proto is not None:
             self.proto.end_checkpoint(self.features)
-        if self.rows is not None:  # one all-gather of the rows serves nn and the knn scores
+        keep = self._ckpts_done == self.kcenter_ckpt
+        # one all-gather of the rows serves nn, the knn scores and the kcenter fill (which alone
+        # needs it at its one checkpoint only)
+        if self.rows is not None and (keep or self.nn is not None or self.knn is not None):
             allf = self.rows.gather(self.features)
+            if keep:
+                # (one rank: `allf` is the feature buffer itself, which the next checkpoint
+                # overwrites)
+                self.kcenter_rows = allf.clone() if allf is self.features else allf
             if self.nn is not None:
                 self.nn.end_checkpoint(self.features, allf)
             if self.knn is not None:
                 self.knn.end_checkpoint(self.features, allf)
+        self._ckpts_done += 1
 
     def _parts(self):
         return [p for p in (self.logit, self.proto, self.nn, self.knn) if p is not None]

@@ -39,7 +39,7 @@ from torch.utils.data import DataLoader, Subset
 
 from . import _capi
 from .loader import load_data
-from .subset_index import write_subset_index
+from .subset_index import json_radius, write_subset_index
 from .synthetic import state_digest
 
 
@@ -67,14 +67,15 @@ def _score_rows(logits, labels, out, bad, score="el2n"):
 
 
 def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect=None,
-                            score="el2n", knn_k=5):
+                            score="el2n", knn_k=5, keep_rows=False):
     """Scores of every example the loader yields, in visit order, plus the visited indices
     (`score`: "el2n" or one of _capi.LOGIT_STATS, from the same logits; or "nn", the distance to
     the nearest visited example of the same class, or "knn" / "knn_disagree", the mean distance
     to the knn_k nearest visited examples and the share of them with another label, from the rows
     `net.linear` consumes).
     A dict given as `collect` receives "labels" (the targets in visit order, int64 on the
-    device) and "num_classes" (the width of the logits), for the class selection policies.
+    device) and "num_classes" (the width of the logits), for the class selection policies, and
+    with keep_rows "rows": the rows `net.linear` consumes, in visit order (the kcenter fill).
 
     Runs `net(input)` exactly as the reference does (:15), so BN follows `net.training`
     (train mode for a freshly built net, as in train.py:59-63).  A label outside [0, C)
@@ -83,7 +84,8 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
     bad = _capi.label_counter(device)
     C = None
     feats, hook = [], None
-    if score in FEATURE_SCORES:  # the classifier's input rows of the same forward
+    by_rows = score in FEATURE_SCORES
+    if by_rows or keep_rows:  # the classifier's input rows of the same forward
         head = getattr(net.module if hasattr(net, "module") else net, "linear", None)
         if not isinstance(head, torch.nn.Linear):
             raise ValueError(f"score={score!r} needs a net whose classifier is `net.linear`")
@@ -99,7 +101,7 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
                     raise ValueError(f"net produces {out.shape[1]} classes, "
                                      f"expected {num_classes}")
                 C = out.shape[1]
-                if hook is None:
+                if not by_rows:
                     s = torch.empty(out.shape[0], dtype=torch.float32, device=out.device)
                     _score_rows(out, target.contiguous(), s, bad, score)
                     scores.append(s)
@@ -109,9 +111,11 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
     finally:
         if hook is not None:
             hook.remove()
-    if hook is not None and visit:
+    if by_rows and visit:
         scores = [_feature_scores(torch.cat(feats).contiguous(), torch.cat(targets), C, score,
                                   knn_k)]
+    if collect is not None and keep_rows:
+        collect["rows"] = torch.cat(feats).contiguous() if feats else None
     if collect is not None:
         collect["labels"] = (torch.cat(targets) if targets
                              else torch.empty(0, dtype=torch.int64, device=device))
@@ -313,10 +317,12 @@ def fast_path(train_loader, net, device):
 
 
 def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, score="el2n",
-                     knn_k=5):
+                     knn_k=5, collect=None):
     """Scores in visit order + visited indices, like el2n_scores_from_loader, on the hand
     kernels: every visit batch of the loader's BatchSampler (all of size B but a ragged last
-    one) is one BN group; chunks of whole batches are gathered + normalised on device."""
+    one) is one BN group; chunks of whole batches are gathered + normalised on device.  A dict
+    given as `collect` receives "rows": the same forward's pooled feature rows in visit order
+    (the kcenter fill)."""
     from . import el2n_fast
     imgs, layout, labs, mean, std = src
     B = train_loader.batch_sampler.batch_size
@@ -340,8 +346,11 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
                     device=dev)
     scores = torch.empty(n, dtype=torch.float32, device=dev)
     bad = _capi.label_counter(dev)
+    by_rows = score in FEATURE_SCORES
     feats = (torch.empty((n, model.linear.in_features), dtype=torch.float32, device=dev)
-             if score in FEATURE_SCORES else None)
+             if by_rows or collect is not None else None)
+    if collect is not None:
+        collect["rows"] = feats
     with torch.inference_mode():
         for c0 in range(0, n, CH):
             c1 = min(n, c0 + CH)
@@ -352,11 +361,15 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
             idx = visit_d[c0:c1]
             _capi.normalize_u8(img_d, mean, std, xb[:rows], index=idx)
             if feats is not None:  # the same forward: its pooled feature rows
-                feats[c0:c1].copy_(el2n_fast.forward_features(model, xb, B, rows)[1][:rows])
-                continue
-            logits = el2n_fast.forward_logits(model, xb, B, rows)[:rows]
+                logits, f = el2n_fast.forward_features(model, xb, B, rows)
+                feats[c0:c1].copy_(f[:rows])
+                if by_rows:
+                    continue
+                logits = logits[:rows]
+            else:
+                logits = el2n_fast.forward_logits(model, xb, B, rows)[:rows]
             _score_rows(logits.contiguous(), lab_d[idx], scores[c0:c1], bad, score)
-        if feats is not None:  # neighbours among the visited examples (LabelError inside)
+        if by_rows:  # neighbours among the visited examples (LabelError inside)
             return _feature_scores(feats, lab_d[visit_d], model.linear.out_features, score,
                                    knn_k), visit_d
     # a label outside [0, C): the reference's one_hot raises (:17), so does this path
@@ -409,7 +422,7 @@ def refine_fast_keep_set(train_loader, src, model, device, scores, visit, sample
 def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size, num_workers,
                   *, dataset=None, subset_index_path=None, return_indices=False,
                   fast: bool = True, refine="auto", policy="global", skip=0, score="el2n",
-                  knn_k=5):
+                  knn_k=5, fill="score", seed_frac=0.0):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
@@ -431,6 +444,12 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     "knn" ranks by the mean distance to the knn_k nearest visited examples of any class and
     "knn_disagree" by the share of those neighbours that carry another label (dd_knn on the same
     rows; knn_k in 1.._capi.KNN_MAX_K, fewer visited examples than knn_k + 1 raise).
+    fill / seed_frac: how the quotas are filled (ScoreConfig.select_fill / kcenter_seed_frac):
+    "score" is the rank cut; "kcenter" seeds every group with its top
+    max(1, floor(seed_frac * quota)) examples by `score` and picks the rest by farthest-first
+    traversal of the visited examples' feature rows (the rows the classifier consumes, from the
+    same single forward; dd_kcenter_greedy), a tie to the earlier visited example.  It needs
+    skip = 0 and is never refined; `sparse_loader.last_selection` records the seeds and radii.
     "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
     over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
     score="el2n"."""
@@ -449,10 +468,13 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
         raise ValueError(f"knn_k must be an integer in 1..{_capi.KNN_MAX_K} (got {knn_k!r})")
     if refine is True and score != "el2n":
         raise ValueError("refine=True re-scores EL2N only: it needs score='el2n'")
-    skip = check_selection(policy, skip, "policy", "skip")
-    default_rule = policy == "global" and skip == 0
+    skip = check_selection(policy, skip, "policy", "skip", fill=fill, seed_frac=seed_frac,
+                           fill_name="fill", frac_name="seed_frac")
+    kcenter = fill == "kcenter"
+    default_rule = policy == "global" and skip == 0 and not kcenter
     if refine is True and not default_rule:
-        raise ValueError("refine=True needs the default selection (policy='global', skip=0)")
+        raise ValueError("refine=True needs the default selection (policy='global', skip=0, "
+                         "fill='score')")
     if torch.device(device).type != "cuda":
         raise ValueError("sparse_loader runs its kernels on a GPU device (libdd.so)")
     module = net.module if hasattr(net, "module") else net
@@ -461,13 +483,15 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     digest = state_digest(module.state_dict()) if subset_index_path else None
     fp = fast_path(train_loader, net, device) if fast else None
     sparse_loader.last_path = "fast" if fp is not None else "general"
+    seen = {} if kcenter else None  # the kcenter fill needs the visited rows
     if fp is not None:
         scores, visit = el2n_scores_fast(train_loader, fp[0], fp[1], device, score=score,
-                                         knn_k=knn_k)
+                                         knn_k=knn_k, collect=seen)
     else:
-        seen = None if policy == "global" else {}  # a class policy needs the visited targets
+        if policy != "global":  # a class policy needs the visited targets
+            seen = {}
         scores, visit = el2n_scores_from_loader(train_loader, net, device, collect=seen,
-                                                score=score, knn_k=knn_k)
+                                                score=score, knn_k=knn_k, keep_rows=kcenter)
     samples = _capi.keep_count(train_samples, sparsity)
     if samples < 0 or samples > scores.numel():
         raise ValueError(f"keep count {samples} outside [0, {scores.numel()}]")
@@ -482,7 +506,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
         else:
             labels_visit, ncls = seen["labels"], seen["num_classes"] or 1
         pos, sparse_loader.last_selection = select_with_policy(
-            scores.contiguous(), labels_visit, ncls, samples, policy, int(skip))
+            scores.contiguous(), labels_visit, ncls, samples, policy, int(skip), fill=fill,
+            seed_frac=seed_frac, rows=seen["rows"] if kcenter else None)
         kept = visit[pos]
     elif fp is not None and refine is True and 0 < samples < scores.numel():
         pos, sparse_loader.last_refine = refine_fast_keep_set(
@@ -510,7 +535,12 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                             **({} if default_rule else {
                                 "select_policy": policy, "select_skip": int(skip),
                                 "class_quota": sparse_loader.last_selection["class_quota"],
-                                "class_skip": sparse_loader.last_selection["class_skip"]})})
+                                "class_skip": sparse_loader.last_selection["class_skip"]}),
+                            **({} if not kcenter else {
+                                "select_fill": fill, "kcenter_seed_frac": float(seed_frac),
+                                "class_seeds": sparse_loader.last_selection["class_seeds"],
+                                "radius": json_radius(
+                                    sparse_loader.last_selection["radius"])})})
     sparse_train_loader = DataLoader(train_subset, batch_size=batch_size, shuffle=True,
                                      num_workers=num_workers)
     if return_indices:

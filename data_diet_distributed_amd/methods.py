@@ -55,11 +55,47 @@ def refinable(method: str) -> bool:
 SELECT_POLICIES = ("global", "stratified", "balanced")
 
 
-def check_selection(policy, skip, policy_name="select_policy", skip_name="select_skip") -> int:
-    """The selection fields of ScoreConfig, and sparse_loader's `policy` / `skip` under their
-    own names: a known policy and an integer skip >= 0 (returned as an int)."""
+def check_selection(policy, skip, policy_name="select_policy", skip_name="select_skip",
+                    fill="score", seed_frac=0.0, *, fill_name="select_fill",
+                    frac_name="kcenter_seed_frac") -> int:
+    """The selection fields of ScoreConfig, and sparse_loader's `policy` / `skip` / `fill` /
+    `seed_frac` under their own names: a known policy, an integer skip >= 0 (returned as an int)
+    and check_fill's conditions on the fill."""
     if policy not in SELECT_POLICIES:
         raise ValueError(f"{policy_name} must be one of {SELECT_POLICIES} (got {policy!r})")
     if isinstance(skip, bool) or not isinstance(skip, (int, np.integer)) or skip < 0:
         raise ValueError(f"{skip_name} must be an integer >= 0 (got {skip!r})")
+    check_fill(fill, seed_frac, int(skip), fill_name=fill_name, frac_name=frac_name,
+               skip_name=skip_name)
     return int(skip)
+
+
+# How the keep-set is filled once the groups and quotas of the policy are fixed:
+#   "score"    the rank cut on the select_by score (every policy above)
+#   "kcenter"  coverage: each group's top max(1, floor(seed_frac * quota)) by the score seed a
+#              farthest-first traversal of the group's feature rows (dd_kcenter_greedy), which
+#              picks the rest: the k-center greedy of Sener & Savarese's core-set selection
+SELECT_FILLS = ("score", "kcenter")
+
+
+def check_fill(fill, seed_frac, skip=0, *, fill_name="select_fill",
+               frac_name="kcenter_seed_frac", skip_name="select_skip") -> float:
+    """ScoreConfig's select_fill / kcenter_seed_frac, and sparse_loader's `fill` / `seed_frac`
+    under their own names: a known fill, a seed fraction in [0, 1] (returned as a float), and no
+    skip with the kcenter fill."""
+    if fill not in SELECT_FILLS:
+        raise ValueError(f"{fill_name} must be one of {SELECT_FILLS} (got {fill!r})")
+    if (isinstance(seed_frac, bool) or not isinstance(seed_frac, (int, float, np.integer,
+                                                                  np.floating))
+            or not 0.0 <= float(seed_frac) <= 1.0):
+        raise ValueError(f"{frac_name} must be a number in [0, 1] (got {seed_frac!r})")
+    if fill == "kcenter" and skip:
+        raise ValueError(f"{fill_name}='kcenter' needs {skip_name}=0 (got {skip!r}): an offset "
+                         f"window is a rank cut's notion")
+    return float(seed_frac)
+
+
+def seed_counts(quotas, seed_frac: float):
+    """Seeds per group of the kcenter fill: max(1, floor(seed_frac * q)) for a quota q > 0, none
+    for q = 0 (never more than q: seed_frac <= 1)."""
+    return [max(1, int(np.floor(float(seed_frac) * int(q)))) if int(q) > 0 else 0 for q in quotas]

@@ -19,6 +19,9 @@ rest (config.DEFAULTS):
   score_checkpoints  K: checkpoint_path/seed{k}/ckpt_{score_epoch}.pth (K = 1: ckpt_E.pth)
   select_policy      global (reference) | stratified | balanced: per-class quotas (--policy)
   select_skip        ranks skipped from the top before the kept window (--skip)
+  select_fill        score (the rank cut) | kcenter: coverage, the greedy k-center fill of the
+                     quotas over the pooled feature rows (--fill); kcenter_seed_frac: the share
+                     of a quota seeded by the score; kcenter_ckpt: whose rows (default: the last)
   bn_mode            EL2N BatchNorm: batch|train (reference) or running|eval
   pegrad_method      auto | direct | ghost             grand_batch   GraNd chunk
   score_gpus         ranks (one per GPU; self-launched here, or run under torchrun)
@@ -138,6 +141,9 @@ def engine_config(cfg):
                        select_policy=str(cfg.get("select_policy", "global")),
                        select_skip=int(cfg.get("select_skip", 0)),
                        knn_k=int(cfg.get("knn_k", 5)),
+                       select_fill=str(cfg.get("select_fill", "score")),
+                       kcenter_seed_frac=float(cfg.get("kcenter_seed_frac", 0.0)),
+                       kcenter_ckpt=int(cfg.get("kcenter_ckpt", -1)),
                        **SCORE_PRECISIONS[prec])
 
 
@@ -149,7 +155,7 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
 
     from . import checkpoints, synthetic
     from .scoring import ScoringEngine
-    from .subset_index import write_subset_index
+    from .subset_index import json_radius, write_subset_index
 
     world, rank, local = launch.rank_env()
     torch.cuda.set_device(local)
@@ -191,6 +197,11 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
         if sel["policy"] != "global" or sel["skip"]:  # (a default run's metadata is unchanged)
             meta.update(select_policy=sel["policy"], select_skip=sel["skip"],
                         class_quota=sel["class_quota"], class_skip=sel["class_skip"])
+        if sel.get("fill") == "kcenter":  # (a run on the score fill: metadata unchanged)
+            meta.update(select_fill=sel["fill"], kcenter_seed_frac=ecfg.kcenter_seed_frac,
+                        kcenter_ckpt=ecfg.kcenter_ckpt % K, select_policy=sel["policy"],
+                        class_quota=sel["class_quota"], class_seeds=sel["class_seeds"],
+                        radius=json_radius(sel["radius"]))
         out_path = out_path or cfg.get("subset_index_path")
         if out_path:
             path = write_subset_index(out_path, kept_np, meta)
@@ -215,6 +226,8 @@ def parse(argv=None):
                     help="keep-set rule (default: select_policy of the config)")
     ap.add_argument("--skip", type=int, default=None,
                     help="ranks skipped from the top (default: select_skip of the config)")
+    ap.add_argument("--fill", default=None, choices=("score", "kcenter"),
+                    help="how the quotas are filled (default: select_fill of the config)")
     return ap.parse_args(argv)
 
 
@@ -225,6 +238,8 @@ def main(argv=None):
         cfg["select_policy"] = args.policy
     if args.skip is not None:
         cfg["select_skip"] = args.skip
+    if args.fill is not None:
+        cfg["select_fill"] = args.fill
     gpus = args.gpus or int(cfg.get("score_gpus", 1))
     if gpus > 1 and not launch.under_launcher():
         rest = list(sys.argv[1:] if argv is None else argv)

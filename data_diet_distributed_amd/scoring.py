@@ -50,7 +50,8 @@ from .forward_scores import (ForwardScores, check_class_sizes,  # noqa: F401
                              check_no_singleton_class, ensemble_mean, nearest_same_class)
 from .methods import (FEATURE_METHODS, FORWARD_FAMILY, FORWARD_SCORES,  # noqa: F401
                       KNN_METHODS, LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS,
-                      SELECT_POLICIES, check_selection, known, pass_of, refinable)
+                      SELECT_FILLS, SELECT_POLICIES, check_fill, check_selection, known,
+                      pass_of, refinable, seed_counts)
 from .resnet import ResNet
 
 MEAN = (0.4914, 0.4822, 0.4465)  # reference data/loader.py:10
@@ -138,6 +139,16 @@ class ScoreConfig:
     # (last_refine stays None).
     select_policy: str = "global"
     select_skip: int = 0
+    # How the groups' quotas are filled (methods.SELECT_FILLS): "score" is the rank cut above;
+    # "kcenter" is coverage: group g (the whole set under "global", a class otherwise) seeds with
+    # its top max(1, floor(kcenter_seed_frac * q_g)) examples by select_by, and farthest-first
+    # traversal of checkpoint kcenter_ckpt's pooled feature rows (an index in [-K, K); the last
+    # by default) picks the other q_g - m_g (select_with_policy; dd_kcenter_greedy).  It needs
+    # select_skip = 0, is never refined (refine=True is rejected, "auto" behaves as False), and
+    # last_selection records the seeds and each group's covering radius.
+    select_fill: str = "score"
+    kcenter_seed_frac: float = 0.0
+    kcenter_ckpt: int = -1
 
     def __post_init__(self):
         self.methods = tuple(self.methods)
@@ -170,10 +181,18 @@ class ScoreConfig:
         if (self.refine_rel < 0 or self.refine_tol <= 0 or self.refine_groups < 1
                 or not 0 < self.refine_max_frac <= 1):
             raise ValueError("refine_rel >= 0, refine_tol > 0, refine_groups >= 1")
-        self.select_skip = check_selection(self.select_policy, self.select_skip)
+        self.select_skip = check_selection(self.select_policy, self.select_skip,
+                                           fill=self.select_fill,
+                                           seed_frac=self.kcenter_seed_frac)
+        self.kcenter_seed_frac = float(self.kcenter_seed_frac)
+        if isinstance(self.kcenter_ckpt, bool) or not isinstance(self.kcenter_ckpt,
+                                                                 (int, np.integer)):
+            raise ValueError(f"kcenter_ckpt must be an integer (got {self.kcenter_ckpt!r})")
+        self.kcenter_ckpt = int(self.kcenter_ckpt)
         if self.refine is True and not self.default_selection():
             raise ValueError("refine=True needs the default selection (select_policy='global', "
-                             "select_skip=0): the refinement re-scores around one threshold")
+                             "select_skip=0, select_fill='score'): the refinement re-scores "
+                             "around one threshold")
         if self.refine is True and not refinable(self.select_by):
             raise ValueError(f"refine=True re-scores EL2N or GraNd only (select_by="
                              f"{self.select_by!r})")
@@ -182,7 +201,8 @@ class ScoreConfig:
         self.el2n_chunk -= self.el2n_chunk % self.batch_size
 
     def default_selection(self) -> bool:
-        return self.select_policy == "global" and self.select_skip == 0
+        return (self.select_policy == "global" and self.select_skip == 0
+                and self.select_fill == "score")
 
 
 def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
@@ -229,7 +249,8 @@ def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
 
 
 def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: str = "global",
-                       skip: int = 0, check_nan: bool = True):
+                       skip: int = 0, check_nan: bool = True, fill: str = "score",
+                       seed_frac: float = 0.0, rows: Optional[torch.Tensor] = None):
     """The keep-set of `k` of the n = keys.numel() examples under a selection policy
     (ScoreConfig.select_policy / select_skip), in dd_select_topk's order: key descending, ties
     by ascending index.  `labels` (int64 [n], on the keys' device) and `num_classes` are read
@@ -238,15 +259,38 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     A class policy costs one small device -> host read (the class counts, from which
     `apportion` makes the per-class skips s and quotas q = apportion(k, n_c - s)) before
     dd_select_topk_by_class runs.  Returns (kept int64 [k] on device, record): the record is
-    {"policy", "skip", "class_counts", "class_skip", "class_quota"} (None x 3 for "global")."""
+    {"policy", "skip", "class_counts", "class_skip", "class_quota"} (None x 3 for "global"),
+    and with the kcenter fill also {"fill", "class_seeds", "radius"}.
+
+    fill="kcenter" (ScoreConfig.select_fill; needs skip = 0 and `rows`, the fp32 [n, D] feature
+    rows of the examples on the keys' device): the groups and quotas are the policy's; group g
+    seeds with its top m_g = seed_counts(q, seed_frac)[g] keys, by the very launches above with
+    the quotas m, and dd_kcenter_greedy picks the other q_g - m_g by farthest-first traversal
+    of the group's rows.  kept = the seeds in the order the score cut returns them, then the
+    picks by (step, group).  "class_seeds" records m (one entry under "global"), "radius" each
+    group's covering radius sqrt(max over its unkept rows of the squared distance to the
+    nearest kept row): 0 where every row is kept, +inf for a group that keeps none of its
+    rows (the artefact's .json records that as null).  The NaN count of the keys, the
+    non-finite rows and the ids are read once, after the loop; any raises ValueError."""
     if policy not in SELECT_POLICIES:
         raise ValueError(f"select policy must be one of {SELECT_POLICIES} (got {policy!r})")
     n, k, skip = keys.numel(), int(k), int(skip)
     if skip < 0 or k < 0 or skip + k > n:
         raise ValueError(f"skip {skip} + keep count {k} outside [0, {n}]")
+    # (a public entry: tools and tests call it without a ScoreConfig in front)
+    seed_frac = check_fill(fill, seed_frac, skip, fill_name="fill", frac_name="seed_frac",
+                           skip_name="skip")
     rec = {"policy": policy, "skip": skip, "class_counts": None, "class_skip": None,
            "class_quota": None}
+    if fill == "kcenter":
+        rec.update(fill=fill, class_seeds=None, radius=None)
+        if rows is None or rows.dim() != 2 or rows.shape[0] != n:
+            raise ValueError(f"fill='kcenter' needs rows [n = {n}, D] (got "
+                             f"{None if rows is None else tuple(rows.shape)})")
     if policy == "global":
+        if fill == "kcenter":
+            return _kcenter_fill(keys, None, [n], [k], rows.contiguous(), seed_frac, rec,
+                                 check_nan)
         kept = _capi.select_topk(keys, skip + k, check_nan=check_nan)[0]
         return (kept[skip:] if skip else kept), rec
     C = int(num_classes)
@@ -258,8 +302,43 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     n_c = host[:C]
     s = apportion(skip, n_c, policy)
     q = apportion(k, [a - b for a, b in zip(n_c, s)], policy)
-    kept = _capi.select_topk_by_class(keys, labels, C, s, q, k_total=k, check=check_nan)[0]
     rec.update(class_counts=n_c, class_skip=s, class_quota=q)
+    if fill == "kcenter":
+        return _kcenter_fill(keys, labels, n_c, q, rows.contiguous(), seed_frac, rec, check_nan)
+    kept = _capi.select_topk_by_class(keys, labels, C, s, q, k_total=k, check=check_nan)[0]
+    return kept, rec
+
+
+def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan):
+    """select_with_policy's kcenter fill over the groups `labels` (None: one group) of `sizes`
+    members with `quotas`; completes and returns (kept, rec)."""
+    G, dev = len(sizes), keys.device
+    m = seed_counts(quotas, seed_frac)
+    if labels is None:
+        seeds, _, nan = _capi.select_topk(keys, m[0], check_nan=False)
+    else:
+        seeds, nan, _ = _capi.select_topk_by_class(keys, labels, G, [0] * G, m, k_total=sum(m),
+                                                   check=False)
+    picks = [q - a for q, a in zip(quotas, m)]
+    picked, _, mind2, stat = _capi.kcenter_greedy(rows, None, labels, sizes, seeds, m, picks,
+                                                  check=False)
+    # by (step, group): the (t, g) with t < picks[g], their positions built on the host (a
+    # boolean mask would make the host wait for the size of its result)
+    p = np.asarray(picks, dtype=np.int64)
+    live = np.flatnonzero(np.arange(picked.shape[0], dtype=np.int64)[:, None] < p[None, :])
+    kept = torch.cat([seeds, picked.flatten().index_select(0, torch.from_numpy(live).to(dev))])
+    # the covering radius per group: the largest squared distance left (kept rows hold -1)
+    far = torch.zeros(G, dtype=torch.float32, device=dev)
+    grp = labels if labels is not None else torch.zeros(keys.numel(), dtype=torch.int64,
+                                                        device=dev)
+    far.scatter_reduce_(0, grp, mind2.clamp(min=0), reduce="amax", include_self=True)
+    # the one read after the loop: the keys' NaN count, the rows' and ids' counts, the radii
+    host = torch.cat([nan.to(torch.float64), stat.to(torch.float64),
+                      far.to(torch.float64)]).tolist()
+    if check_nan and host[0]:
+        raise ValueError(f"{int(host[0])} NaN score(s): the keep-set is undefined")
+    _capi.check_kcenter(host[1:3])
+    rec.update(class_seeds=m, radius=[float(np.sqrt(v)) for v in host[3:]])
     return kept, rec
 
 
@@ -460,6 +539,14 @@ class ScoringEngine:
     def __init__(self, models: List[ResNet], cfg: ScoreConfig, device):
         if not models:
             raise ValueError("need at least one checkpoint model")
+        if cfg.select_fill == "kcenter":
+            if not -len(models) <= cfg.kcenter_ckpt < len(models):
+                raise ValueError(f"kcenter_ckpt={cfg.kcenter_ckpt} outside [-{len(models)}, "
+                                 f"{len(models)}): {len(models)} checkpoint(s)")
+            if "el2n" not in map(pass_of, cfg.methods):
+                raise ValueError("select_fill='kcenter' takes its feature rows from the EL2N "
+                                 "forward: request at least one score of that forward "
+                                 f"(methods={cfg.methods})")
         self.models = models
         self.cfg = cfg
         self.device = torch.device(device)
@@ -491,13 +578,17 @@ class ScoringEngine:
         self._wss: Dict[int, torch.Tensor] = {}  # pegrad workspace per lane
         self.last_refine: Optional[dict] = None  # what the last run()'s _refine did
         # the last run()'s selection: {"policy", "skip", "class_counts", "class_skip",
-        # "class_quota"} (select_with_policy's record)
+        # "class_quota"}, with the kcenter fill also {"fill", "class_seeds", "radius"}
+        # (select_with_policy's record)
         self.last_selection: Optional[dict] = None
         # set when a GraNd forward on fp16 operand halves overflowed and the engine re-scored
         # on bf16 halves (run(); the engine keeps bf16 GraNd packs from then on)
         self.grand_fallback: Optional[str] = None
         self.fallback: Dict[str, str] = {}  # method -> why it was re-scored on bf16 halves
         self._bad = None  # the last score_shard's count of labels outside [0, C)
+        # the kcenter fill's feature rows of the whole dataset (checkpoint kcenter_ckpt's, from
+        # the last score_shard)
+        self._kcenter_rows: Optional[torch.Tensor] = None
         # optional heartbeat, called with a short message every `progress_every` launch chunks
         # (a long config-5 pass otherwise prints nothing for minutes)
         self.progress = None
@@ -735,7 +826,11 @@ class ScoringEngine:
         self._bad = _capi.label_counter(self.device)
         # everything the EL2N forward produces shares one forward per checkpoint and chunk
         fwd = ForwardScores(cfg, labels[lo:hi], self.models[0].linear, group,
-                            counter=self._bad if kinds[0] == "el2n" else None)
+                            counter=self._bad if kinds[0] == "el2n" else None,
+                            # (no EL2N pass: _validate's re-scoring of GraNd alone, which
+                            # leaves the rows of the first scoring in place)
+                            kcenter_ckpt=(cfg.kcenter_ckpt % K if cfg.select_fill == "kcenter"
+                                          and "el2n" in kinds else None))
         grand = (torch.zeros(n, dtype=torch.float32, device=self.device)
                  if "grand" in kinds else None)
 
@@ -771,6 +866,8 @@ class ScoringEngine:
                         t.record_stream(st)
                     main.wait_stream(st)
         done = fwd.finalize(K)
+        if fwd.kcenter_rows is not None:
+            self._kcenter_rows = fwd.kcenter_rows
         if grand is not None:
             done["grand"] = ensemble_mean(grand, K)
         out = {m: done[m] for m in cfg.methods}  # (run() gathers the vectors in this order)
@@ -897,7 +994,8 @@ class ScoringEngine:
                 all_labels = gather_scores(labels.contiguous(), N, B, group)
             kept, self.last_selection = select_with_policy(
                 keys, all_labels, self.models[0].linear.out_features, k, c.select_policy,
-                c.select_skip, check_nan)
+                c.select_skip, check_nan, fill=c.select_fill, seed_frac=c.kcenter_seed_frac,
+                rows=self._kcenter_rows if c.select_fill == "kcenter" else None)
             return kept
 
         full, kept, k = sharded_job(score, N, B, sparsity, self.cfg.select_by, select,

@@ -36,6 +36,12 @@ def write_subset_index(path: str, indices, meta: dict | None = None) -> str:
     return stem + ".npy"
 
 
+def json_radius(radius):
+    """A kcenter selection's radii for the metadata: +inf (a group that keeps none of its rows)
+    becomes None, which JSON writes as null (`Infinity` is no JSON token)."""
+    return [float(r) if np.isfinite(r) else None for r in radius]
+
+
 def read_subset_index(path: str):
     stem = _stem(path)
     idx = np.load(stem + ".npy", allow_pickle=False)

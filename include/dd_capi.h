@@ -759,6 +759,65 @@ int dd_knn(const float* q, const int64_t* q_id, const int64_t* q_label, int64_t 
            float* mean_dist, float* disagree, float* accum_dist, float* accum_disagree,
            void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Greedy k-center (farthest-first traversal; Sener & Savarese's core-set baseline) over feature
+ * rows, inside groups: the coverage keep-set.  Purely additive: dd_abi_version() stays 10.
+ *
+ * rows fp32 [n][D] in GROUP ORDER: group g is rows [off[g], off[g + 1]) (off int64 [G + 1] on the
+ * device, ascending, off[G] <= n), in ascending id inside a group (ids int64 [n], distinct inside
+ * a group, 0 <= id < 2^31).  seeds int64: POSITIONS of rows, group g's at
+ * [seed_off[g], seed_off[g + 1]) (seed_off int64 [G + 1] on the device), each inside its group;
+ * max_seeds is the longest list (host).  picks int64 [G] on the device: the rows group g takes
+ * after its seeds, seeds + picks <= the group's size; steps = max(picks) (host: the loop bound).
+ *
+ *   d2(i, c)  = sum_d (rows[i][d] - rows[c][d])^2, in fp32 from the fp32 rows, never
+ *               |a|^2 + |b|^2 - 2 ab: an exact duplicate is at exactly 0, and on small-integer
+ *               rows every sum is exact.  The order of the additions is fixed by D alone (lane l
+ *               of a wave takes columns 256 j + 4 l + 0..3 in ascending order into one fma chain,
+ *               then a fixed butterfly).
+ *   mind2[i]  = min over the kept rows c of i's group of d2(i, c); -1 for a kept row; +inf in a
+ *               group that keeps nothing
+ *   step t of group g (t < picks[g]) takes the not-yet-kept row with the largest mind2, a tie to
+ *   the smaller id:   picked[t][g] = its id,  radius2[t][g] = its mind2 at that moment
+ *   and (t, g) with t >= picks[g]: picked = -1, radius2 = -1.  A kept row is never taken again.
+ *   bad[0] += the rows with a NaN or infinite element (the caller clears it, and rejects the
+ *   call's results when it is non-zero).
+ *
+ * Launches (all on `stream`, nothing read back, no allocation): one init; ceil(max_seeds / S) seed
+ * launches, each folding up to S centres per group, staged in LDS, into rows read once (S =
+ * seed_batch, 0: 8, capped so that S centres fit 48 KB); steps + 1 pick launches, launch t
+ * folding the centre that launch t - 1 published and publishing one candidate per workgroup with a
+ * 64-bit atomic maximum on (bits(mind2) << 32) | ~position into slot [t][g] of the workspace; one
+ * finish launch.  The launch boundaries are the only ordering between workgroups: no kernel waits
+ * for another workgroup.  `blocks`: workgroups per group (0: from n and G alone).
+ *
+ * Invariance: a d2 is a function of the two rows and D alone and min / max are order-independent,
+ * so every output is bitwise independent of seed_batch, blocks, the rows' alignment, the other
+ * groups and their layout, and of whether a centre arrives as a seed or as a pick.
+ *
+ * Limits: 0 <= n < 2^31, 1 <= D <= 4096, 1 <= G <= DD_KCENTER_MAX_GROUPS, 0 <= steps,
+ * max_seeds <= n, 0 <= seed_batch <= DD_KCENTER_MAX_SEED_BATCH, 0 <= blocks <=
+ * DD_KCENTER_MAX_BLOCKS; outside them, a NULL buffer the call would touch or
+ * a workspace below dd_kcenter_workspace_bytes (host only; 0 for bad arguments; 8 max(steps, 1) G
+ * bytes rounded up to 256) is DD_EINVAL with a message before any launch.  n == 0 returns DD_OK.
+ * ---------------------------------------------------------------------------------------- */
+#define DD_KCENTER_MAX_SEED_BATCH 64
+#define DD_KCENTER_MAX_BLOCKS 4096
+#define DD_KCENTER_MAX_GROUPS 65535
+
+size_t dd_kcenter_workspace_bytes(int64_t n, int32_t D, int32_t G, int64_t steps);
+
+/* The centres one seed launch folds per group for this D and `seed_batch` as passed to
+ * dd_kcenter_greedy (host only; 0 for bad arguments). */
+int32_t dd_kcenter_seed_batch(int32_t D, int32_t seed_batch);
+
+int dd_kcenter_greedy(const float* rows, const int64_t* ids, int64_t n, int32_t D,
+                      const int64_t* off, int32_t G, const int64_t* seeds,
+                      const int64_t* seed_off, int64_t max_seeds, const int64_t* picks,
+                      int64_t steps, int32_t seed_batch, int32_t blocks, int64_t* picked,
+                      float* radius2, float* mind2, int32_t* bad, void* workspace,
+                      size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
