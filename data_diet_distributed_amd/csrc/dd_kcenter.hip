@@ -28,16 +28,16 @@
 // launch geometry, the group layout, the other rows, the seed batch, the rows' alignment (a row
 // that is not 16-byte aligned is read with scalar loads into the SAME lanes) or on whether the
 // centre arrives as a seed or as a pick; min and max are order-independent.
-#include "dd_common.h"
-
-#include <math.h>
+#include "dd_feat.h"
 
 namespace dd {
 namespace kcenter {
 
-constexpr int kThreads = 256;
+using feat::align256;
+using feat::kMaxD;
+using feat::kThreads;
+
 constexpr int kWaves = kThreads / kWave;
-constexpr int kMaxD = 4096;           // dd_linear_forward's bound
 constexpr int kPass = 4 * kWave;      // columns a wave covers with one 16-byte load per lane
 constexpr int kSeedLds = 48 * 1024;   // bytes of staged centres per seed workgroup, at most
 constexpr int kMaxSeedBatch = DD_KCENTER_MAX_SEED_BATCH;
@@ -45,8 +45,6 @@ constexpr int kMaxBlocks = DD_KCENTER_MAX_BLOCKS;
 constexpr int kMaxGroups = DD_KCENTER_MAX_GROUPS;
 constexpr int kTargetBlocks = 1024;   // workgroups of one launch the automatic count aims at
 constexpr int kCheckBlocks = 256;     // workgroups per group from which the slot is read first
-
-__host__ __device__ constexpr int64_t align256(int64_t v) { return (v + 255) / 256 * 256; }
 
 // passes of 256 columns, rounded up to a power of two (the row's registers: 4 NP per lane)
 static int passes_of(int D) {
@@ -128,13 +126,10 @@ __global__ __launch_bounds__(kThreads) void init_kernel(const float* __restrict_
   const int lane = threadIdx.x % kWave;
   const int64_t row = (int64_t)blockIdx.x * kWaves + threadIdx.x / kWave;
   if (row >= n) return;  // (a whole wave)
-  const float* __restrict__ x = rows + row * (int64_t)D;
-  float nf = 0.f;
-  for (int d = lane; d < D; d += kWave) nf = fabsf(x[d]) < INFINITY ? nf : 1.f;  // NaN or +-inf
-  nf = group_max<kWave>(nf);
+  const bool nonfinite = feat::wave_row_nonfinite(rows + row * (int64_t)D, D, lane);
   if (lane == 0) {
     mind2[row] = INFINITY;
-    if (nf != 0.f) atomicAdd(bad, 1);
+    if (nonfinite) atomicAdd(bad, 1);
   }
 }
 

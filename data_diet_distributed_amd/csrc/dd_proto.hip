@@ -14,15 +14,16 @@
 // any of it is added.  It accumulates in registers while the class stays the same and issues one
 // global 64-bit atomic per column when the class changes and at the end of its run: about
 // (n / rows-per-workgroup + C) D atomics with `order` sorted by label, instead of n D.
-#include "dd_common.h"
-
-#include <math.h>
+#include "dd_feat.h"
 
 namespace dd {
 namespace proto {
 
-constexpr int kThreads = 256;
-constexpr int kMaxD = 4096;             // dd_linear_forward's bound
+using feat::kMaxD;
+using feat::kRows;
+using feat::kThreads;
+using feat::wave_row_sqdist;
+
 constexpr int64_t kMaxC = 1ll << 20;    // dd_select_topk_by_class's bound
 constexpr float kRange = 32768.f;       // |v| < 2^15: |q(v)| < 2^39
 constexpr double kScale = 16777216.0;   // 2^24
@@ -144,11 +145,8 @@ __global__ __launch_bounds__(kThreads) void centroids_kernel(
   }
 }
 
-// one row per wave64, ROWS rows per block (dd_logit_scores' mid-width dispatch).  Lane l takes
-// columns l, l + 64, ... in ascending order with scalar loads (no alignment-dependent path), then
-// the fixed butterfly: the order of the additions depends on D alone.
-constexpr int kRows = kThreads / kWave;
-
+// one row per wave64 (dd_logit_scores' mid-width dispatch), reduced by feat::wave_row_sqdist:
+// scalar loads (no alignment-dependent path), an order of additions that depends on D alone
 __global__ __launch_bounds__(kThreads) void proto_scores_kernel(
     const float* __restrict__ feat, const int64_t* __restrict__ labels,
     const float* __restrict__ centroids, int64_t B, int D, int64_t C, float* __restrict__ score,
@@ -158,19 +156,11 @@ __global__ __launch_bounds__(kThreads) void proto_scores_kernel(
   if (row >= B) return;  // (a whole wave: the shuffles below stay within one wave)
   const int64_t y = labels[row];
   const bool bad_label = y < 0 || y >= C;
-  const float* __restrict__ x = feat + row * (int64_t)D;
-  const float* __restrict__ mu = centroids + (bad_label ? 0 : y) * (int64_t)D;
-  float s = 0.f, nf = 0.f;
-  for (int d = lane; d < D; d += kWave) {
-    const float v = x[d];
-    const float diff = v - mu[d];
-    s = fmaf(diff, diff, s);
-    nf = fabsf(v) < INFINITY ? nf : 1.f;  // NaN or +-inf
-  }
-  s = group_sum<kWave>(s);
-  nf = group_max<kWave>(nf);
+  bool bad;
+  const float s = wave_row_sqdist(feat + row * (int64_t)D,
+                                  centroids + (bad_label ? 0 : y) * (int64_t)D, D, lane, true, &bad);
   if (lane == 0) {
-    const float r = (bad_label || nf != 0.f) ? __builtin_nanf("") : sqrtf(s);
+    const float r = (bad_label || bad) ? __builtin_nanf("") : sqrtf(s);
     if (score) score[row] = r;
     if (accum) accum[row] += r;
   }

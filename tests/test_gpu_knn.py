@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from data_diet_distributed_amd import _capi
+from test_gpu_nn import run_nn
 from test_knn_scores import KS, check_picks, gap_floor, ref_knn
 from test_nn_scores import CASES, TINY, make_set, value_bound
 
@@ -173,6 +174,32 @@ def test_bitwise_invariance(cuda, sets):
                            {"shift": 3, "splits": 7, "c_perm": rng.permutation(n)}):
                     got = run_knn(cuda, f, labels, k, operands, **kw)
                     assert same_bits(got, one), (name, operands, k, sorted(kw))
+
+
+@pytest.mark.parametrize("name", ("d512", "d100", "d17"))
+def test_k1_is_nn_same_class_over_one_class(cuda, sets, name):
+    """The key of a pair and the value of a distance have one definition (csrc/dd_feat.h): with
+    every row in one class, dd_nn_same_class's dist and nn_id are dd_knn(k = 1)'s first column
+    bit for bit, whatever the split count; on three identical rows (exactly 0, the smallest other
+    id) and on a row with a NaN (NaN and -1 as a query, never picked) too."""
+    f = sets[name][0].copy()
+    n, D = f.shape
+    t = (1, n // 2, n - 2)
+    f[t[1]] = f[t[0]]
+    f[t[2]] = f[t[0]]
+    nan_row = n // 3
+    f[nan_row, D // 2] = np.nan
+    one_class = np.zeros(n, np.int64)
+    for operands in OPERANDS:
+        dist, nn_id = run_nn(cuda, f, one_class, 1, operands)
+        assert [dist[i] for i in t] == [0.0, 0.0, 0.0]
+        assert [int(nn_id[i]) for i in t] == [t[1], t[0], t[0]]
+        assert np.isnan(dist[nan_row]) and nn_id[nan_row] == -1
+        assert not np.any(nn_id == nan_row)
+        for splits in (1, 3):
+            got = run_knn(cuda, f, one_class, 1, operands, splits=splits)
+            assert np.array_equal(got["dist"][:, 0].view(np.uint32), dist.view(np.uint32))
+            assert np.array_equal(got["nbr_id"][:, 0], nn_id)
 
 
 def test_accumulators_accumulate_and_outputs_are_optional(cuda, sets):

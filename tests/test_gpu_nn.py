@@ -172,6 +172,24 @@ def test_bitwise_invariance(cuda, sets):
                 assert np.array_equal(i, one[1]), (name, kw)
 
 
+@pytest.mark.parametrize("name", ("d512", "d100", "d17"))
+def test_dist_is_the_proto_score_against_the_pick(cuda, sets, name):
+    """The value of a distance has one definition (the row reducer of csrc/dd_feat.h):
+    dd_proto_scores with the candidate rows as centroids and every row labelled with the position
+    of its nn pick gives nn's dist bit for bit."""
+    f, labels, C, _ = sets[name]
+    c_order, _ = class_order(labels, C)
+    pos = np.empty(len(f), np.int64)  # id -> position among the candidates
+    pos[c_order] = np.arange(len(f))
+    q, c = torch.from_numpy(f).to(cuda), torch.from_numpy(f[c_order]).to(cuda)
+    for operands in OPERANDS:
+        dist, nn_id = run_nn(cuda, f, labels, C, operands)
+        assert np.all(nn_id >= 0)  # (no class of one in these sets: every row has a pick)
+        score = torch.full((len(f),), -7.0, dtype=torch.float32, device=cuda)
+        _capi.proto_scores(q, torch.from_numpy(pos[nn_id]).to(cuda), c, score=score)
+        assert np.array_equal(score.cpu().numpy().view(np.uint32), dist.view(np.uint32))
+
+
 def test_accum_accumulates_and_outputs_are_optional(cuda, sets):
     f, labels, C, _ = sets["d64"]
     dist, _ = run_nn(cuda, f, labels, C)
