@@ -490,7 +490,11 @@ __device__ __forceinline__ void split4(float4 v, bf16x4& hi, bf16x4& lo) {
 // (One wave per SIMD with 9 tap accumulators.  Two tap groups of 4 waves, 5 / 4 accumulators
 // and two waves per SIMD, measured 0.76x at 32x32 and 0.90x on the persistent 16x16 kernel,
 // profiles/r04_conv/ab_pegrad_tg2_rejected.txt: the second wave re-reads the B fragments and
-// the LDS traffic per MFMA rises, which costs more than the hidden latency gains.)
+// the LDS traffic per MFMA rises, which costs more than the hidden latency gains.  Two waves
+// per SIMD do pay where the second wave brings its own 32 outputs and shares the staged
+// activations: pegrad_direct3x3w_kernel, the 64 c x 128 o workgroup of the persistent 16-wide
+// form, same LDS reads per MFMA and half the activation staging per MFMA; 216 -> 182 us at
+// 128 -> 128 and 169 -> 110 us on the 64 -> 128 head per bench launch, profiles/pegrad_wide.)
 template <int W, int STR>
 __global__ __launch_bounds__(256, 1) void pegrad_direct3x3_kernel(
     const float* __restrict__ act, const float* __restrict__ gout, int cin, int cout, int H,
@@ -1020,6 +1024,296 @@ static void launch_direct3x3p(const float* act, const float* gout, int64_t B, in
       act, gout, cin, cout, H, ncb, nob, col_scale, partial, (int)total);
 }
 
+// The persistent kernel on a 64 c x 128 o workgroup: 8 waves as 2 (c) x 4 (o), two per SIMD.
+// A wide tile is two logical 64 x 64 tiles, o-blocks 2j and 2j + 1 of one c-block: the
+// activation ring (the expensive side: three shifted split copies per row) is staged once for
+// both, each thread staging half of what a 4-wave workgroup's thread does, and the gradient
+// stage holds 128 o.  Every wave keeps pegrad_direct3x3p_kernel's 32 c x 32 o x 9 tap
+// accumulators, its product order (hi*hi, hi*lo, lo*hi per sub-step) and its square-and-sum,
+// and the workgroup writes the two logical tiles' partials from the same four waves in the
+// same order, so `partial` is bitwise what the 64 x 64 kernel writes.  With an odd n_oblk the
+// last wide tile's second half is all padding and writes nothing.
+// Two waves per SIMD leave 256 registers a wave, 144 of them accumulators: the A fragments
+// are read one tap ahead of their MFMAs (the second wave of the SIMD covers the latency)
+// instead of a sub-step ahead, and a step's staging goes in pieces behind the taps of
+// sub-step 1.
+template <int W, int STR>
+struct D3WCfg {
+  using C = D3Cfg<W, STR>;
+  static constexpr int NTH = 512;
+  static constexpr int OW = 128;                    // outputs per workgroup
+  static constexpr int GPLANE = OW * C::GCS;
+  static constexpr int G_BYTES = 2 * 2 * GPLANE;    // [buf][hi|lo][o][t]
+  static constexpr int LDS = C::ACT_BYTES + G_BYTES;
+  static constexpr int NA = C::NEW * 64 * C::WI / 4 / NTH;   // activation float4: a step
+  static constexpr int NAW = C::WIN * 64 * C::WI / 4 / NTH;  // ... a tile's first window
+  static constexpr int NGT = OW * 8 / NTH;                   // gradient float4 per thread
+  static_assert(C::NEW * 64 * C::WI / 4 % NTH == 0 && C::WIN * 64 * C::WI / 4 % NTH == 0,
+                "whole float4 rounds");
+  static_assert(LDS + 32 <= 160 * 1024, "LDS budget");
+};
+
+template <int W, int STR>
+__global__ __launch_bounds__(512, 1) void pegrad_direct3x3w_kernel(
+    const float* __restrict__ act, const float* __restrict__ gout, int cin, int cout, int H,
+    int n_cblk, int n_oblk, const float* __restrict__ col_scale, float* __restrict__ partial,
+    int total) {
+  using C = D3Cfg<W, STR>;
+  using CW = D3WCfg<W, STR>;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  char* act_lds = smem;
+  char* g_lds = smem + C::ACT_BYTES;
+  float* red = reinterpret_cast<float*>(smem + CW::LDS);  // 8 floats past the staging
+
+  const int n_wblk = (n_oblk + 1) / 2;
+  const int per_ex = n_cblk * n_oblk, per_exw = n_cblk * n_wblk;
+  const int HW = H * W;                       // output positions
+  const int HI = STR * H, HWI = HI * C::WI;    // input rows, positions
+  int pidx, c0, o0;   // pidx: the partial of the tile's first half
+  bool second;        // the second half is a logical tile (its o-block < n_oblk)
+  const float *a_b, *g_b;
+  auto set_tile = [&](int t) {
+    const int lid = (int)xcd_remap((unsigned)t, (unsigned)total);
+    const int b = lid / per_exw;
+    const int rem = lid - b * per_exw;
+    const int cb = rem / n_wblk, j = rem - cb * n_wblk;
+    c0 = cb * 64;
+    o0 = j * CW::OW;
+    pidx = b * per_ex + cb * n_oblk + 2 * j;
+    second = 2 * j + 1 < n_oblk;
+    a_b = act + (size_t)b * cin * HWI;
+    g_b = gout + (size_t)b * cout * HW;
+  };
+
+  constexpr int NTH = CW::NTH;
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int wc = wv & 1, wo = wv >> 1, r = lane & 31, h = lane >> 5;  // 2 (c) x 4 (o) waves
+
+  // ---- staging, as pegrad_direct3x3p_kernel: unconditional loads from clamped addresses,
+  // out-of-range values zeroed by a mask when they are converted
+  constexpr int NGT = CW::NGT;
+  float4 ra[CW::NAW], rg[NGT];
+  bool va[CW::NAW], vg[NGT];
+  auto load_act = [&](auto NKc, int ir0) {
+    constexpr int NK = decltype(NKc)::value;
+#pragma unroll
+    for (int k = 0; k < NK; ++k) {
+      const int idx = tid + NTH * k;
+      const int x4 = idx % C::TPR, c = (idx / C::TPR) % 64, rr = idx / (C::TPR * 64);
+      const int ir = ir0 + rr;
+      const int cg = c0 + c;
+      va[k] = ir >= 0 && ir < HI && cg < cin;
+      const int irc = ir < 0 ? 0 : (ir >= HI ? HI - 1 : ir);
+      const int cgc = cg < cin ? cg : cin - 1;
+      ra[k] = *reinterpret_cast<const float4*>(a_b + (size_t)cgc * HWI + irc * C::WI + x4 * 4);
+    }
+  };
+  auto load_g = [&](int tstep) {
+    const int ts = tstep < HW / 32 ? tstep : HW / 32 - 1;  // last step prefetches a dummy
+#pragma unroll
+    for (int k = 0; k < NGT; ++k) {
+      const int idx = tid + NTH * k;
+      const int o = idx >> 3, t4 = idx & 7;
+      const int og = o0 + o;
+      vg[k] = og < cout;
+      const int ogc = og < cout ? og : cout - 1;
+      rg[k] = *reinterpret_cast<const float4*>(g_b + (size_t)ogc * HW + ts * 32 + t4 * 4);
+    }
+  };
+  // one activation float4 (k folds) into its slot's three shifted split copies
+  auto store_act = [&](int k, int ir0) {
+    const int idx = tid + NTH * k;
+    const int x4 = idx % C::TPR, c = (idx / C::TPR) % 64, rr = idx / (C::TPR * 64);
+    const int slot = (ir0 + rr + 1) % C::S;
+    const float4 v = conv::keep_if(ra[k], va[k]);
+    if constexpr (STR == 1) {
+      static_assert(C::TPR <= 16 && 16 % C::TPR == 0, "row of lanes inside a DPP row");
+      uint2 hs[3], ls[3];
+      conv::split_shift3(v, x4 == 0, x4 == C::TPR - 1, hs, ls);
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        char* base = act_lds + ((slot * 3 + kx) * 2) * C::PLANE + c * C::CS + x4 * 8;
+        *reinterpret_cast<uint2*>(base) = hs[kx];
+        *reinterpret_cast<uint2*>(base + C::PLANE) = ls[kx];
+      }
+    } else {
+      float left = conv::lane_prev<C::TPR>(v.w);
+      if (x4 == 0) left = 0.f;
+      // input columns 4 x4 - 1 .. 4 x4 + 3 -> decimated columns 2 x4, 2 x4 + 1 of image kx
+      const float f[5] = {left, v.x, v.y, v.z, v.w};
+      __bf16 hv[5], lv[5];
+#pragma unroll
+      for (int i = 0; i < 5; ++i) {
+        hv[i] = (__bf16)f[i];
+        lv[i] = (__bf16)(f[i] - (float)hv[i]);
+      }
+      typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+      for (int kx = 0; kx < 3; ++kx) {
+        char* base = act_lds + ((slot * 3 + kx) * 2) * C::PLANE + c * C::CS + x4 * 4;
+        *reinterpret_cast<bf16x2*>(base) = bf16x2{hv[kx], hv[kx + 2]};
+        *reinterpret_cast<bf16x2*>(base + C::PLANE) = bf16x2{lv[kx], lv[kx + 2]};
+      }
+    }
+  };
+  auto store_g = [&](int k, int gbuf) {
+    const int idx = tid + NTH * k;
+    const int o = idx >> 3, t4 = idx & 7;
+    bf16x4 hi, lo;
+    split4(conv::keep_if(rg[k], vg[k]), hi, lo);
+    char* base = g_lds + ((gbuf * 2) * CW::OW + o) * C::GCS + t4 * 8;
+    *reinterpret_cast<bf16x4*>(base) = hi;
+    *reinterpret_cast<bf16x4*>(base + CW::GPLANE) = lo;
+  };
+  // a tile's first window (input rows -1 .. WIN - 2) and its step-0 gradients
+  const std::integral_constant<int, CW::NA> KN;
+  const std::integral_constant<int, CW::NAW> KW;
+  auto load_window = [&]() {
+    load_act(KW, -1);
+    load_g(0);
+  };
+  auto store_window = [&]() {
+#pragma unroll
+    for (int k = 0; k < CW::NAW; ++k) store_act(k, -1);
+#pragma unroll
+    for (int k = 0; k < NGT; ++k) store_g(k, 0);
+  };
+
+  constexpr int NTAP = 9;  // one accumulator per tap
+  floatx16 acc[NTAP];
+
+  const int nsteps = H / C::R;
+  int t = blockIdx.x;
+  set_tile(t);
+  load_window();
+  store_window();
+  __syncthreads();
+
+  // one fragment: B hi / lo (T < 0) or tap T's A hi / lo, of sub-step s
+  auto frag = [&](int y0, int gbuf, int s, int t, int lo) -> bf16x8 {
+    const int tl = 16 * s + 8 * h;
+    const int ro = tl / W, x = tl % W;
+    if (t < 0) {
+      const char* gb = g_lds + ((gbuf * 2) * CW::OW + wo * 32 + r) * C::GCS + tl * 2;
+      return *reinterpret_cast<const bf16x8*>(gb + lo * CW::GPLANE);
+    }
+    const int ky = t / 3, kx = t % 3;
+    const int slot = (STR * (y0 + ro) + ky) % C::S;
+    const char* ab = act_lds + ((slot * 3 + kx) * 2) * C::PLANE + (wc * 32 + r) * C::CS + x * 2;
+    return *reinterpret_cast<const bf16x8*>(ab + lo * C::PLANE);
+  };
+  // one step; LAST: the tile's last step, which prefetches the next tile's first window
+  // (when there is one) instead of this tile's next rows, and stages nothing
+  auto step = [&](int st, auto LASTc, bool has_next) {
+    constexpr bool LAST = decltype(LASTc)::value;
+    const int y0 = st * C::R;
+    const int inext = STR * y0 + C::WIN - 1;  // first input row past this step's window
+    if constexpr (!LAST) {
+      load_act(KN, inext);
+      load_g(st + 1);
+    } else {
+      if (has_next) load_window();  // the tile vars already name the next tile
+    }
+    const int gbuf = st & 1;
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+      bf16x8 ah[NTAP], al[NTAP];
+      const bf16x8 bh = frag(y0, gbuf, s, -1, 0), bl = frag(y0, gbuf, s, -1, 1);
+      ah[0] = frag(y0, gbuf, s, 0, 0);
+      al[0] = frag(y0, gbuf, s, 0, 1);
+#pragma unroll
+      for (int i = 0; i < NTAP; ++i) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (i + 1 < NTAP) {  // the next tap's fragments, read under this tap's MFMAs
+          ah[i + 1] = frag(y0, gbuf, s, i + 1, 0);
+          al[i + 1] = frag(y0, gbuf, s, i + 1, 1);
+        }
+        floatx16 a = acc[i];
+        a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bh, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah[i], bl, a, 0, 0, 0);
+        a = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al[i], bh, a, 0, 0, 0);
+        acc[i] = a;
+        // the next step's rows are converted and staged a float4 per tap behind sub-step 1's
+        // MFMAs (those slots / the other gradient buffer are not read in this step)
+        if constexpr (!LAST) {
+          if (s == 1 && i < CW::NA) store_act(i, inext);
+          else if (s == 1 && i < CW::NA + NGT) store_g(i - CW::NA, gbuf ^ 1);
+        }
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    __syncthreads();
+  };
+  static_assert(CW::NA + NGT <= NTAP, "a staging piece per tap");
+
+  for (;;) {
+#pragma unroll
+    for (int i = 0; i < NTAP; ++i) acc[i] = floatx16{0};
+    for (int st = 0; st + 1 < nsteps; ++st) step(st, std::false_type{}, false);
+    // the last step: switch the tile variables to the next tile first (its window loads
+    // issue under this step's MFMAs); this tile's output index and column scales are kept
+    const int pidx_c = pidx, o0_c = o0;
+    const bool second_c = second;
+    const int tn = t + (int)gridDim.x;
+    const bool has_next = tn < total;
+    if (has_next) set_tile(tn);
+    step(nsteps - 1, std::true_type{}, has_next);
+
+    const int o = o0_c + wo * 32 + r;  // C/D column = lane & 31
+    float s2 = (o < cout) ? 1.f : 0.f;
+    if (col_scale && o < cout) {
+      const float sc = col_scale[o];
+      s2 = sc * sc;
+    }
+    float v = 0.f;
+#pragma unroll
+    for (int i = 0; i < NTAP; ++i)
+#pragma unroll
+      for (int k = 0; k < 16; ++k) v += acc[i][k] * acc[i][k];
+    v = wave_sum(v * s2);
+    if (lane == 0) red[wv] = v;
+    // the next tile's window and step-0 gradients into LDS (every wave passed the last
+    // step's barrier, so no slot is being read)
+    if (has_next) store_window();
+    __syncthreads();
+    // waves 0-3 are the first logical tile's (wc, wo) waves in its order, waves 4-7 the second's
+    if (tid == 0) partial[pidx_c] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (tid == 256 && second_c) partial[pidx_c + 1] = (red[4] + red[5]) + (red[6] + red[7]);
+    if (!has_next) break;
+    __syncthreads();  // red is rewritten by the next tile
+    t = tn;
+  }
+}
+
+template <int W, int STR>
+static void launch_direct3x3w(const float* act, const float* gout, int64_t B, int cin, int cout,
+                              int H, const float* col_scale, float* partial, hipStream_t st) {
+  using CW = D3WCfg<W, STR>;
+  const int ncb = (int)ceil_div(cin, 64), nob = (int)ceil_div(cout, 64);
+  constexpr int LDS = CW::LDS + 32;  // + the 8 partial sums
+  static bool attr_set = false;
+  if (!attr_set) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&pegrad_direct3x3w_kernel<W, STR>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, LDS);
+    attr_set = true;
+  }
+  const int64_t total = B * ncb * ((nob + 1) / 2);
+  const int64_t grid = std::min<int64_t>(total, device_cus());
+  pegrad_direct3x3w_kernel<W, STR><<<(unsigned)grid, CW::NTH, LDS, st>>>(
+      act, gout, cin, cout, H, ncb, nob, col_scale, partial, (int)total);
+}
+
+// The 64 c x 128 o workgroup of the persistent 16-wide kernels needs two o-blocks to share a
+// staged activation ring.  DD_PEGRAD_WIDE (read per call, for A/B runs): 0 keeps the 64 x 64
+// tile, 1 takes the wide tile wherever cout > 64; unset, an even number of o-blocks takes it
+// (an odd one would run a half-empty last tile per c-block).
+static bool direct3x3_wide(int cout) {
+  const int nob = (int)ceil_div(cout, 64);
+  if (nob < 2) return false;
+  const int v = env_int("DD_PEGRAD_WIDE", kEnvUnset);
+  return v == kEnvUnset ? nob % 2 == 0 : v != 0;
+}
+
 static bool direct3x3_ok(const dd_conv_geom* g) {
   if (g->kh != 3 || g->kw != 3 || g->pad != 1) return false;
   if (g->stride == 1)
@@ -1230,12 +1524,19 @@ int dd_conv_pegrad_sqnorm(const float* act, const float* gout, const dd_conv_geo
     pgram_q_launch(act, gout, geom, col_scale, partial, st);
   } else if (p.d3x3) {
     // the kernel's H is the output height (= the input height at stride 1)
-    if (geom->stride == 2)
+    const bool wide = direct3x3_wide(geom->cout);
+    if (geom->stride == 2 && wide)
+      launch_direct3x3w<16, 2>(act, gout, B, geom->cin, geom->cout, geom->ho, col_scale, partial,
+                               st);
+    else if (geom->stride == 2)
       launch_direct3x3p<16, 2>(act, gout, B, geom->cin, geom->cout, geom->ho, col_scale, partial,
                                st);
     else if (geom->w == 32)
       launch_direct3x3<32, 1>(act, gout, B, geom->cin, geom->cout, geom->h, col_scale, partial,
                               st);
+    else if (geom->w == 16 && wide)
+      launch_direct3x3w<16, 1>(act, gout, B, geom->cin, geom->cout, geom->h, col_scale, partial,
+                               st);
     else if (geom->w == 16)
       launch_direct3x3p<16, 1>(act, gout, B, geom->cin, geom->cout, geom->h, col_scale, partial,
                                st);
