@@ -669,7 +669,11 @@ __global__ __launch_bounds__(256, (NA == 1 && (WO == 2 || MODE != 3)) ? 2 : 1) v
 #define DD_C1_LIST(F_, NA_, WO_) DD_C1_LIST1(F_, NA_, WO_, false) DD_C1_LIST1(F_, NA_, WO_, true)
 // the specialised epilogues (MODE 0, float4): (XF, F16, EPI).  Both operand types: the EL2N
 // statistics (with and without the producer's BN + ReLU staged; the fused unit-input kernels
-// use this epilogue, and the separate pass they replace must round its sums alike).  fp16:
+// use this epilogue, and the separate pass they replace must round its sums alike: the sums of
+// squares are left to the compiler's contraction, which fuses them here (fma, the first two
+// squares of a row joined in the other order) and not in the run-time-flag kernel (mul +
+// packed add), so DD_C1_EPI=0 changes the last bits of the statistics partials -- y is
+// bitwise equal either way; tests/test_gpu_conv_knobs.py holds both to float64).  fp16:
 // the GraNd forward's conv1 (folded BN: bias + ReLU) and projection (bias); bf16: the GraNd backward (conv3^T mask, conv1^T residual +
 // mask or up2 residual + mask, the projection's plain ^T).  Measured (tools/ab_conv.py --kernel
 // c1x1, profiles/r05_s7/c1x1_epi/): 1.04-1.31x with statistics, up to 1.34x on the plain 64 ->

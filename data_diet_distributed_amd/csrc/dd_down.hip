@@ -1179,14 +1179,21 @@ static int launch_fwd_pw(FwdArgs a, hipStream_t st) {
   return DD_OK;
 }
 
-// the compile-time epilogue of a launch with the shortcut fused (down_fwd_kernel EPI): 1 / 2
-// for the EL2N / GraNd flag sets, 0 otherwise or with DD_DOWN_EPI=0 (the runtime-flag kernel)
-static int fwd_epi(const Out& m, const Out& s) {
-  static const int f = env_int("DD_DOWN_EPI", 1);
-  if (f == 0 || !s.y) return 0;
+// the flag set of a launch with the shortcut fused: 1 / 2 for the EL2N / GraNd sets, else 0
+static int fwd_flags(const Out& m, const Out& s) {
+  if (!s.y) return 0;
   if (!m.bias && !m.relu && m.stats && !s.bias && !s.relu && s.stats) return 1;
   if (m.bias && m.relu && !m.stats && s.bias && !s.relu && !s.stats) return 2;
   return 0;
+}
+// its compile-time epilogue (down_fwd_kernel EPI): the flag set, or 0 (the runtime-flag
+// kernel) with DD_DOWN_EPI=0.  The fused unit input exists on the EL2N epilogue only and keeps
+// it whatever the knob says (it is accepted by its flag set, fwd_flags).  The two epilogues
+// write bitwise the same y; their statistics partials differ in the last bits (the sums of
+// squares are left to the compiler's contraction; tests/test_gpu_conv_knobs.py)
+static int fwd_epi(const Out& m, const Out& s) {
+  static const int f = env_int("DD_DOWN_EPI", 1);
+  return f == 0 ? 0 : fwd_flags(m, s);
 }
 // four waves along o (128-output workgroups) where the padded outputs fill them: 1.13-1.26x
 // the 2 x 2 layout on the three ResNet-18 heads, bit-identical (tools/ab_conv.py --kernel down,
@@ -1394,7 +1401,7 @@ static int down_forward_impl(const float* x, int64_t B, int32_t cin, int32_t ho,
     // run-time epilogue for anything else
     const int wa = down::fwd_wa(cout);
     const int epi = down::fwd_epi(a.main, a.sc);  // 1: EL2N statistics, 2: GraNd bias + ReLU
-    DD_REQUIRE(!xres || (sc && epi == 1),
+    DD_REQUIRE(!xres || (sc && down::fwd_flags(a.main, a.sc) == 1),
                "dd_down_forward_unit_input: the unit form needs the fused shortcut and "
                "statistics on both outputs");
     DD_REQUIRE(!in_scale || xres || !sc,
@@ -1424,7 +1431,7 @@ static int down_forward_impl(const float* x, int64_t B, int32_t cin, int32_t ho,
     const int wa = down::fwd_wa(cout);
 #define DD_DOWN_X(WO_, RB_, E_)                                                          \
     if (xres) {                                                                          \
-      DD_REQUIRE(sc && down::fwd_epi(a.main, a.sc) == 1,                                 \
+      DD_REQUIRE(sc && down::fwd_flags(a.main, a.sc) == 1,                               \
                  "dd_down_forward_unit_input: the unit form needs the fused shortcut and " \
                  "statistics on both outputs");                                          \
       return wa == 4 ? down::launch_fwd<WO_, RB_, E_, true, 4, 1, down::kXmUnit>(a, st) \

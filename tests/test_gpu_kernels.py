@@ -408,6 +408,36 @@ def test_pgram_q_ignores_ablation_env(cuda, monkeypatch):
                                    atol=1e-7 * max(1.0, ref.max()))
 
 
+def test_pgq_knob_sends_auto_to_pgram_q(cuda, monkeypatch):
+    """DD_PGQ=1 (read per call): AUTO resolves to the quarter-tiled Gram kernel at 16x16 and
+    gives bitwise what GHOST gives there; unset or 0, AUTO keeps another kernel."""
+    act, gout, k, s, p = _conv_case(cuda, (9, 17, 16, 16, 33, 3, 1, 1), 7)
+    ref = o_pegrad.conv_pegrad_sqnorm(act, gout, k, k, s, p)
+    a, g = torch.from_numpy(act).to(cuda), torch.from_numpy(gout).to(cuda)
+    geom = _capi.conv_geom(a, g, (k, k), s, p)
+
+    def run(method):
+        ws = torch.empty(max(_capi.conv_workspace_bytes(geom, method, "bf16x3"), 4),
+                         dtype=torch.uint8, device=cuda)
+        sq = torch.zeros(9, device=cuda)
+        _capi.conv_pegrad_sqnorm(a, g, (k, k), s, p, sq, ws, method=method, precision="bf16x3")
+        return sq.cpu()
+
+    for off in (None, "0"):
+        monkeypatch.delenv("DD_PGQ", raising=False)
+        if off is not None:
+            monkeypatch.setenv("DD_PGQ", off)
+        assert _capi.conv_method(geom, "auto", "bf16x3") != "pgram_q"
+    default = run("auto")
+    ghost = run("ghost")
+    monkeypatch.setenv("DD_PGQ", "1")
+    assert _capi.conv_method(geom, "auto", "bf16x3") == "pgram_q"
+    assert torch.equal(run("auto"), ghost)
+    for out in (default, ghost):
+        np.testing.assert_allclose(out.numpy().astype(np.float64), ref, rtol=1e-4,
+                                   atol=1e-7 * max(1.0, ref.max()))
+
+
 # ---- BN affine per-example gradient norm (grand_params: all) ----------------------------------
 @pytest.mark.parametrize("B,C,H,W,res", [(5, 64, 32, 32, False), (3, 128, 16, 16, True),
                                          (4, 256, 8, 8, False), (6, 512, 4, 4, True),
