@@ -282,6 +282,48 @@ def _opt(t, dtype, name, numel=None):
     return p
 
 
+def _ptr(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def _same_shape(name, t, shape):
+    if t is not None and tuple(t.shape) != shape:
+        raise ValueError(f"{name} must be {shape}")
+
+
+def _residual_like(residual, y_prev):
+    if residual is not None:
+        _dev(residual, torch.float32, "residual")
+        if residual.shape != y_prev.shape:
+            raise ValueError("residual must match y_prev")
+
+
+def _affine_ptrs(pair, G, C, names, per="cin", optional=False):
+    """Pointers of a grouped BN (scale, shift) pair [G, C] (optional: two NULLs for None)."""
+    if optional and pair is None:
+        return None, None
+    scale, shift = pair
+    for name, t in zip(names, (scale, shift)):
+        _dev(t, torch.float32, name)
+        if t.numel() != G * C:
+            raise ValueError(f"{name} must have G*{per} = {G * C} entries")
+    return _ptr(scale), _ptr(shift)
+
+
+def _groups(B, group_size, needed, what="in_affine / stats"):
+    """(group_size or 0, number of groups) of a launch whose `what` needs groups."""
+    gs = int(group_size) if group_size is not None else 0
+    if needed and gs <= 0:
+        raise ValueError(f"group_size is required with {what}")
+    return gs, -(-B // gs) if needed else 1
+
+
+def _n_stat(n_stat, B):
+    """Rows that enter the statistics, clamped to [0, B] (the library clamps alike, so a
+    caller's out-of-range value reaches no kernel either way)."""
+    return B if n_stat is None else min(max(int(n_stat), 0), B)
+
+
 # ---- input feed ------------------------------------------------------------------------------
 def normalize_u8(img: torch.Tensor, mean, std, out: torch.Tensor, index: torch.Tensor = None):
     """out = (img / 255 - mean) / std  (reference data/loader.py:8-11).  img uint8 [n,C,H,W]
@@ -1118,6 +1160,44 @@ def _stats_buffer(buf, G, C, tiles, device):
     return buf
 
 
+# The four layouts of a conv's BN partials (BNStats of nst valid rows over G groups of gs).
+def _stats3x3(buf, G, gs, nst, C, h, w, device):
+    """3x3: one partial per 32 consecutive positions of a group (two images at 4x4)."""
+    tiles = conv3x3_tiles_per_group(h, w, gs)
+    ipt = max(1, 32 // (h * w))
+    return BNStats(_stats_buffer(buf, G, C, tiles, device), G, gs, nst, tiles, ipt,
+                   tiles // (gs // ipt), C, h * w)
+
+
+def _stats_gemm(what, G, gs, nst, C, ho, wo, device):
+    """1x1 / implicit GEMM: position-granular partials (one per 64 consecutive positions of
+    the group)."""
+    tiles = int(lib().dd_conv1x1_tiles_per_group(ho, wo, gs))
+    if tiles < 0:
+        raise DDError(f"no {what} stats layout for {ho}x{wo} with group_size {gs}")
+    return BNStats(_stats_buffer(None, G, C, tiles, device), G, gs, nst, tiles, -64, 1, C,
+                   ho * wo)
+
+
+def _stats_head(shortcut, G, gs, nst, C, ho, wo, device):
+    """Downsampling head: per-tile partials, four images per tile at 4x4; (the 3x3 conv's,
+    the fused shortcut's or None), each with its own buffer."""
+    tiles = int(lib().dd_down_tiles_per_group(ho, wo, gs))
+    if tiles < 0:
+        raise DDError(f"no downsample tile geometry for {ho}x{wo} with group_size {gs}")
+    ipt = 4 if (ho, wo) == (4, 4) else 1
+    geom = (G, gs, nst, tiles, ipt, tiles // (gs // ipt), C, ho * wo)
+    return (BNStats(_stats_buffer(None, G, C, tiles, device), *geom),
+            BNStats(_stats_buffer(None, G, C, tiles, device), *geom) if shortcut else None)
+
+
+def _stats_stem7(G, gs, nst, C, h, w, device):
+    """7x7 stem: one image per tile."""
+    tiles = int(lib().dd_stem7_tiles_per_group(h, w, gs))
+    return BNStats(_stats_buffer(None, G, C, tiles, device), G, gs, nst, tiles, 1, tiles // gs,
+                   C, (h // 2) * (w // 2))
+
+
 def conv3x3(x: torch.Tensor, packed: torch.Tensor, out_channels: int, bias=None, residual=None,
             mask_src=None, relu=False, out=None, in_affine=None, in_relu=True, group_size=None,
             stats=False, n_stat=None, stats_buf=None, mask_out=None, mask_in=None):
@@ -1134,39 +1214,20 @@ def conv3x3(x: torch.Tensor, packed: torch.Tensor, out_channels: int, bias=None,
     shape = (B, out_channels, h, w)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    for name, t in (("residual", residual), ("mask_src", mask_src), ("out", out)):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}")
-    grouped = in_affine is not None or stats
-    gs = int(group_size) if group_size is not None else 0
-    if grouped and gs <= 0:
-        raise ValueError("group_size is required with in_affine / stats")
-    G = -(-B // gs) if grouped else 1
-    sc = sh = None
-    if in_affine is not None:
-        sc, sh = in_affine
-        for name, t in (("in_scale", sc), ("in_shift", sh)):
-            _dev(t, torch.float32, name)
-            if t.numel() != G * cin:
-                raise ValueError(f"{name} must have G*cin = {G * cin} entries")
-    st = None
-    nst = B if n_stat is None else int(n_stat)
-    if stats:
-        tiles = conv3x3_tiles_per_group(h, w, gs)
-        sbuf = _stats_buffer(stats_buf, G, out_channels, tiles, x.device)
-        # one partial per 32 consecutive positions of a group (two images at 4x4)
-        ipt = max(1, 32 // (h * w))
-        st = BNStats(sbuf, G, gs, min(max(nst, 0), B), tiles, ipt, tiles // (gs // ipt),
-                     out_channels, h * w)
+    _same_shape("residual", residual, shape)
+    _same_shape("mask_src", mask_src, shape)
+    _same_shape("out", out, shape)
+    gs, G = _groups(B, group_size, in_affine is not None or stats)
+    sc, sh = _affine_ptrs(in_affine, G, cin, ("in_scale", "in_shift"), optional=True)
+    nst = _n_stat(n_stat, B)
+    st = _stats3x3(stats_buf, G, gs, nst, out_channels, h, w, x.device) if stats else None
     e0 = _t0(x)
     rc = lib().dd_conv3x3_forward(_dev(x, torch.float32, "x"), B, cin, h, w,
                                   ctypes.c_void_p(packed.data_ptr()), out_channels,
                                   _opt(bias, torch.float32, "bias", out_channels),
                                   _opt(residual, torch.float32, "residual"),
                                   _opt(mask_src, torch.float32, "mask_src"), int(bool(relu)),
-                                  _opt(sc, torch.float32, "in_scale"),
-                                  _opt(sh, torch.float32, "in_shift"), int(bool(in_relu)),
-                                  gs, nst, ctypes.c_void_p(st.buf.data_ptr()) if st else None,
+                                  sc, sh, int(bool(in_relu)), gs, nst, _ptr(st.buf) if st else None,
                                   _mask_ptr(mask_out, B, out_channels, h, w),
                                   _mask_ptr(mask_in, B, out_channels, h, w),
                                   _dev(out, torch.float32, "out"), pack_operands(packed),
@@ -1203,24 +1264,11 @@ def conv3x3_unit_input(y_prev: torch.Tensor, affine, packed: torch.Tensor, out_c
     B, cin, h, w = y_prev.shape
     gs = int(group_size)
     G = -(-B // gs)
-    scale, shift = affine
-    for name, t in (("scale", scale), ("shift", shift)):
-        _dev(t, torch.float32, name)
-        if t.numel() != G * cin:
-            raise ValueError(f"{name} must have G*cin = {G * cin} entries")
-    if residual is not None:
-        _dev(residual, torch.float32, "residual")
-        if residual.shape != y_prev.shape:
-            raise ValueError("residual must match y_prev")
-    rs = rt = None
-    if res_affine is not None:
-        if residual is None:
-            raise ValueError("res_affine needs residual")
-        rs, rt = res_affine
-        for name, t in (("res_scale", rs), ("res_shift", rt)):
-            _dev(t, torch.float32, name)
-            if t.numel() != G * cin:
-                raise ValueError(f"{name} must have G*cin = {G * cin} entries")
+    scale, shift = _affine_ptrs(affine, G, cin, ("scale", "shift"))
+    _residual_like(residual, y_prev)
+    if res_affine is not None and residual is None:
+        raise ValueError("res_affine needs residual")
+    rs, rt = _affine_ptrs(res_affine, G, cin, ("res_scale", "res_shift"), optional=True)
     if x_out is None:
         x_out = torch.empty_like(y_prev)
     elif x_out.shape != y_prev.shape:
@@ -1228,21 +1276,14 @@ def conv3x3_unit_input(y_prev: torch.Tensor, affine, packed: torch.Tensor, out_c
     shape = (B, out_channels, h, w)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=y_prev.device)
-    elif tuple(out.shape) != shape:
-        raise ValueError(f"out must be {shape}")
-    nst = B if n_stat is None else int(n_stat)
-    tiles = conv3x3_tiles_per_group(h, w, gs)
-    sbuf = _stats_buffer(stats_buf, G, out_channels, tiles, y_prev.device)
-    ipt = max(1, 32 // (h * w))
-    st = BNStats(sbuf, G, gs, min(max(nst, 0), B), tiles, ipt, tiles // (gs // ipt),
-                 out_channels, h * w)
+    _same_shape("out", out, shape)
+    nst = _n_stat(n_stat, B)
+    st = _stats3x3(stats_buf, G, gs, nst, out_channels, h, w, y_prev.device)
     e0 = _t0(y_prev)
     rc = lib().dd_conv3x3_forward_unit_input(
-        _dev(y_prev, torch.float32, "y_prev"), _dev(scale, torch.float32, "scale"),
-        _dev(shift, torch.float32, "shift"), _opt(residual, torch.float32, "residual"),
-        _opt(rs, torch.float32, "res_scale"), _opt(rt, torch.float32, "res_shift"),
+        _dev(y_prev, torch.float32, "y_prev"), scale, shift, _ptr(residual), rs, rt,
         _dev(x_out, torch.float32, "x_out"), B, cin, h, w, ctypes.c_void_p(packed.data_ptr()),
-        out_channels, gs, nst, ctypes.c_void_p(sbuf.data_ptr()), _dev(out, torch.float32, "out"),
+        out_channels, gs, nst, _ptr(st.buf), _dev(out, torch.float32, "out"),
         pack_operands(packed), pack_acc_scale(packed), _stream(y_prev))
     _check(rc, "dd_conv3x3_forward_unit_input")
     # the conv's bytes plus the residual read and the unit output written
@@ -1258,7 +1299,7 @@ def channel_stats(y: torch.Tensor, group_size: int, n_stat=None, stats_buf=None)
     B, C, h, w = y.shape
     G = -(-B // group_size)
     sbuf = _stats_buffer(stats_buf, G, C, group_size, y.device)
-    nst = B if n_stat is None else min(max(int(n_stat), 0), B)
+    nst = _n_stat(n_stat, B)
     rc = lib().dd_channel_stats(_dev(y, torch.float32, "y"), B, C, h * w, int(group_size), nst,
                                 ctypes.c_void_p(sbuf.data_ptr()), _stream(y))
     _check(rc, "dd_channel_stats")
@@ -1293,18 +1334,12 @@ def bn_apply_maxpool(y: torch.Tensor, affine, group_size: int) -> torch.Tensor:
     _dev(y, torch.float32, "y", 4)
     B, C, h, w = y.shape
     G = -(-B // group_size)
-    scale, shift = affine
-    for name, t in (("scale", scale), ("shift", shift)):
-        _dev(t, torch.float32, name)
-        if t.numel() != G * C:
-            raise ValueError(f"{name} must have G*C = {G * C} entries")
+    scale, shift = _affine_ptrs(affine, G, C, ("scale", "shift"), per="C")
     out = torch.empty((B, C, (h - 1) // 2 + 1, (w - 1) // 2 + 1), dtype=torch.float32,
                       device=y.device)
     e0 = _t0(y)
     rc = lib().dd_bn_apply_maxpool(_dev(y, torch.float32, "y"), B, C, h, w, int(group_size),
-                                   _dev(scale, torch.float32, "scale"),
-                                   _dev(shift, torch.float32, "shift"),
-                                   _dev(out, torch.float32, "out"), _stream(y))
+                                   scale, shift, _dev(out, torch.float32, "out"), _stream(y))
     _check(rc, "dd_bn_apply_maxpool")
     _t1(e0, "bn_apply", 4.0 * (y.numel() + out.numel()), y, tag="maxpool")
     return out
@@ -1317,11 +1352,7 @@ def bn_apply(y: torch.Tensor, affine, group_size: int, residual=None, res_affine
     _dev(y, torch.float32, "y", 4)
     B, C, h, w = y.shape
     G = -(-B // group_size)
-    scale, shift = affine
-    for name, t in (("scale", scale), ("shift", shift)):
-        _dev(t, torch.float32, name)
-        if t.numel() != G * C:
-            raise ValueError(f"{name} must have G*C = {G * C} entries")
+    scale, shift = _affine_ptrs(affine, G, C, ("scale", "shift"), per="C")
     if residual is not None:
         _dev(residual, torch.float32, "residual")
         if residual.shape != y.shape:
@@ -1333,8 +1364,7 @@ def bn_apply(y: torch.Tensor, affine, group_size: int, residual=None, res_affine
         out = torch.empty_like(y)
     e0 = _t0(y)
     rc = lib().dd_bn_apply(_dev(y, torch.float32, "y"), B, C, h * w, int(group_size),
-                           _dev(scale, torch.float32, "scale"), _dev(shift, torch.float32, "shift"),
-                           _opt(residual, torch.float32, "residual"),
+                           scale, shift, _opt(residual, torch.float32, "residual"),
                            _opt(rs, torch.float32, "res_scale", G * C),
                            _opt(rt, torch.float32, "res_shift", G * C), int(bool(res_relu)),
                            int(bool(relu)), _opt(out if write_out else None, torch.float32, "out"),
@@ -1357,32 +1387,15 @@ def conv1x1(x: torch.Tensor, packed: torch.Tensor, out_channels: int, stride: in
     shape = (B, out_channels, ho, wo)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    for name, t in (("residual", residual), ("mask_src", mask_src), ("out", out)):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}")
+    _same_shape("residual", residual, shape)
+    _same_shape("mask_src", mask_src, shape)
+    _same_shape("out", out, shape)
     if res_up2 is not None and tuple(res_up2.shape) != (B, out_channels, ho // 2, wo // 2):
         raise ValueError("res_up2 must be [B, cout, ho/2, wo/2]")
-    grouped = in_affine is not None or stats
-    gs = int(group_size) if group_size is not None else 0
-    if grouped and gs <= 0:
-        raise ValueError("group_size is required with in_affine / stats")
-    G = -(-B // gs) if grouped else 1
-    sc = sh = None
-    if in_affine is not None:
-        sc, sh = in_affine
-        for name, t in (("in_scale", sc), ("in_shift", sh)):
-            _dev(t, torch.float32, name)
-            if t.numel() != G * cin:
-                raise ValueError(f"{name} must have G*cin = {G * cin} entries")
-    st = None
-    nst = B if n_stat is None else min(max(int(n_stat), 0), B)
-    if stats:
-        tiles = int(lib().dd_conv1x1_tiles_per_group(ho, wo, gs))
-        if tiles < 0:
-            raise DDError(f"no 1x1 stats layout for {ho}x{wo} with group_size {gs}")
-        # position-granular partials (one per 64 consecutive positions of the group)
-        st = BNStats(_stats_buffer(None, G, out_channels, tiles, x.device), G, gs, nst, tiles,
-                     -64, 1, out_channels, ho * wo)
+    gs, G = _groups(B, group_size, in_affine is not None or stats)
+    sc, sh = _affine_ptrs(in_affine, G, cin, ("in_scale", "in_shift"), optional=True)
+    nst = _n_stat(n_stat, B)
+    st = _stats_gemm("1x1", G, gs, nst, out_channels, ho, wo, x.device) if stats else None
     e0 = _t0(x)
     rc = lib().dd_conv1x1_forward(_dev(x, torch.float32, "x"), B, cin, h, w, int(stride),
                                   ctypes.c_void_p(packed.data_ptr()), out_channels,
@@ -1390,9 +1403,8 @@ def conv1x1(x: torch.Tensor, packed: torch.Tensor, out_channels: int, stride: in
                                   _opt(residual, torch.float32, "residual"),
                                   _opt(res_up2, torch.float32, "res_up2"),
                                   _opt(mask_src, torch.float32, "mask_src"), int(bool(relu)),
-                                  _opt(sc, torch.float32, "in_scale"),
-                                  _opt(sh, torch.float32, "in_shift"), int(bool(in_relu)), gs,
-                                  nst, ctypes.c_void_p(st.buf.data_ptr()) if st else None,
+                                  sc, sh, int(bool(in_relu)), gs, nst,
+                                  _ptr(st.buf) if st else None,
                                   _dev(out, torch.float32, "out"), pack_operands(packed),
                                   pack_acc_scale(packed), _stream(x))
     _check(rc, "dd_conv1x1_forward")
@@ -1415,35 +1427,23 @@ def conv1x1_unit_input(y_prev: torch.Tensor, affine, packed: torch.Tensor, out_c
     if gs <= 0:
         raise ValueError("group_size must be positive")
     G = -(-B // gs)
-    sc, sh = affine
-    rs = rt = None
-    if res_affine is not None:
-        if residual is None:
-            raise ValueError("res_affine needs residual")
-        rs, rt = res_affine
-    for name, t in (("scale", sc), ("shift", sh), ("res_scale", rs), ("res_shift", rt)):
-        if t is not None:
-            _dev(t, torch.float32, name)
-            if t.numel() != G * cin:
-                raise ValueError(f"{name} must have G*cin = {G * cin} entries")
+    if res_affine is not None and residual is None:
+        raise ValueError("res_affine needs residual")
+    sc, sh = _affine_ptrs(affine, G, cin, ("scale", "shift"))
+    rs, rt = _affine_ptrs(res_affine, G, cin, ("res_scale", "res_shift"), optional=True)
     if residual is not None and tuple(residual.shape) != tuple(y_prev.shape):
         raise ValueError("residual must have y_prev's shape")
     xout = torch.empty_like(y_prev)
     out = torch.empty((B, out_channels, h, w), dtype=torch.float32, device=y_prev.device)
-    tiles = int(lib().dd_conv1x1_tiles_per_group(h, w, gs))
-    if tiles < 0:
-        raise DDError(f"no 1x1 stats layout for {h}x{w} with group_size {gs}")
-    nst = B if n_stat is None else min(max(int(n_stat), 0), B)
-    st = BNStats(_stats_buffer(None, G, out_channels, tiles, y_prev.device), G, gs, nst, tiles,
-                 -64, 1, out_channels, h * w)
+    nst = _n_stat(n_stat, B)
+    st = _stats_gemm("1x1", G, gs, nst, out_channels, h, w, y_prev.device)
     e0 = _t0(y_prev)
     rc = lib().dd_conv1x1_forward_unit_input(
-        _dev(y_prev, torch.float32, "y_prev"), _dev(sc, torch.float32, "scale"),
-        _dev(sh, torch.float32, "shift"), _opt(residual, torch.float32, "residual"),
-        _opt(rs, torch.float32, "res_scale"), _opt(rt, torch.float32, "res_shift"),
-        _dev(xout, torch.float32, "xout"), B, cin, h, w, ctypes.c_void_p(packed.data_ptr()),
-        out_channels, gs, nst, ctypes.c_void_p(st.buf.data_ptr()), _dev(out, torch.float32, "y"),
-        pack_operands(packed), pack_acc_scale(packed), _stream(y_prev))
+        _dev(y_prev, torch.float32, "y_prev"), sc, sh, _opt(residual, torch.float32, "residual"),
+        rs, rt, _dev(xout, torch.float32, "xout"), B, cin, h, w,
+        ctypes.c_void_p(packed.data_ptr()), out_channels, gs, nst, _ptr(st.buf),
+        _dev(out, torch.float32, "y"), pack_operands(packed), pack_acc_scale(packed),
+        _stream(y_prev))
     _check(rc, "dd_conv1x1_forward_unit_input")
     _t1(e0, "conv1x1_unit", 2.0 * B * h * w * cin * out_channels, y_prev, tag="stats",
         nbytes=_conv_bytes(B, cin, h, w, out_channels, h, w, 1, 1)
@@ -1529,17 +1529,14 @@ def stem7(x: torch.Tensor, packed: torch.Tensor, out_channels: int, group_size: 
     gs = int(group_size)
     if not stem7_supported(h, w, cin, out_channels, gs):
         raise DDError(f"no stem7 geometry for {cin} -> {out_channels} at {h}x{w}")
-    G = -(-B // gs)
-    tiles = int(lib().dd_stem7_tiles_per_group(h, w, gs))
+    nst = _n_stat(n_stat, B)
+    st = _stats_stem7(-(-B // gs), gs, nst, out_channels, h, w, x.device)
     ho, wo = h // 2, w // 2
     y = torch.empty((B, out_channels, ho, wo), dtype=torch.float32, device=x.device)
-    nst = B if n_stat is None else min(max(int(n_stat), 0), B)
-    st = BNStats(_stats_buffer(None, G, out_channels, tiles, x.device), G, gs, nst, tiles, 1,
-                 tiles // gs, out_channels, ho * wo)
     e0 = _t0(x)
     rc = lib().dd_stem7_forward(_dev(x, torch.float32, "x"), B, h, w,
                                 ctypes.c_void_p(packed.data_ptr()), out_channels, gs, nst,
-                                ctypes.c_void_p(st.buf.data_ptr()), _dev(y, torch.float32, "y"),
+                                _ptr(st.buf), _dev(y, torch.float32, "y"),
                                 pack_operands(packed), pack_acc_scale(packed), _stream(x))
     _check(rc, "dd_stem7_forward")
     _t1(e0, "stem7", 2.0 * B * ho * wo * 147 * out_channels, x,
@@ -1576,37 +1573,19 @@ def conv_gemm(x: torch.Tensor, packed: torch.Tensor, out_channels: int, kernel_s
     shape = (B, out_channels, ho, wo)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=x.device)
-    for name, t in (("residual", residual), ("out", out)):
-        if t is not None and tuple(t.shape) != shape:
-            raise ValueError(f"{name} must be {shape}")
-    grouped = in_affine is not None or stats
-    gs = int(group_size) if group_size is not None else 0
-    if grouped and gs <= 0:
-        raise ValueError("group_size is required with in_affine / stats")
-    G = -(-B // gs) if grouped else 1
-    sc = sh = None
-    if in_affine is not None:
-        sc, sh = in_affine
-        for name, t in (("in_scale", sc), ("in_shift", sh)):
-            _dev(t, torch.float32, name)
-            if t.numel() != G * cin:
-                raise ValueError(f"{name} must have G*cin = {G * cin} entries")
-    st = None
-    nst = B if n_stat is None else min(max(int(n_stat), 0), B)
-    if stats:
-        tiles = int(lib().dd_conv1x1_tiles_per_group(ho, wo, gs))
-        if tiles < 0:
-            raise DDError(f"no GEMM-conv stats layout for {ho}x{wo} with group_size {gs}")
-        st = BNStats(_stats_buffer(None, G, out_channels, tiles, x.device), G, gs, nst, tiles,
-                     -64, 1, out_channels, ho * wo)
+    _same_shape("residual", residual, shape)
+    _same_shape("out", out, shape)
+    gs, G = _groups(B, group_size, in_affine is not None or stats)
+    sc, sh = _affine_ptrs(in_affine, G, cin, ("in_scale", "in_shift"), optional=True)
+    nst = _n_stat(n_stat, B)
+    st = _stats_gemm("GEMM-conv", G, gs, nst, out_channels, ho, wo, x.device) if stats else None
     e0 = _t0(x)
     rc = lib().dd_conv_gemm_forward(_dev(x, torch.float32, "x"), B, cin, h, w, kh, kw,
                                     int(stride), int(padding), ctypes.c_void_p(packed.data_ptr()),
                                     out_channels, _opt(bias, torch.float32, "bias", out_channels),
                                     _opt(residual, torch.float32, "residual"), int(bool(relu)),
-                                    _opt(sc, torch.float32, "in_scale"),
-                                    _opt(sh, torch.float32, "in_shift"), int(bool(in_relu)), gs,
-                                    nst, ctypes.c_void_p(st.buf.data_ptr()) if st else None,
+                                    sc, sh, int(bool(in_relu)), gs, nst,
+                                    _ptr(st.buf) if st else None,
                                     _dev(out, torch.float32, "out"), pack_operands(packed),
                                     pack_acc_scale(packed), _stream(x))
     _check(rc, "dd_conv_gemm_forward")
@@ -1658,29 +1637,17 @@ def conv_down(x: torch.Tensor, packed3x3: torch.Tensor, out_channels: int, packe
     shape = (B, out_channels, ho, wo)
     y = torch.empty(shape, dtype=torch.float32, device=x.device)
     ys = torch.empty(shape, dtype=torch.float32, device=x.device) if packed1x1 is not None else None
-    gs = int(group_size) if group_size is not None else 0
-    if stats and gs <= 0:
-        raise ValueError("group_size is required with stats")
-    st = sts = None
-    nst = B if n_stat is None else min(max(int(n_stat), 0), B)
-    if stats:
-        G = -(-B // gs)
-        tiles = int(lib().dd_down_tiles_per_group(ho, wo, gs))
-        if tiles < 0:
-            raise DDError(f"no downsample tile geometry for {ho}x{wo} with group_size {gs}")
-        ipt = 4 if (ho, wo) == (4, 4) else 1
-        mk = lambda: BNStats(_stats_buffer(None, G, out_channels, tiles, x.device), G, gs, nst,  # noqa: E731
-                             tiles, ipt, tiles // (gs // ipt), out_channels, ho * wo)
-        st = mk()
-        sts = mk() if ys is not None else None
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    gs, G = _groups(B, group_size, stats, "stats")
+    nst = _n_stat(n_stat, B)
+    st, sts = (_stats_head(ys is not None, G, gs, nst, out_channels, ho, wo, x.device)
+               if stats else (None, None))
     e0 = _t0(x)
-    rc = lib().dd_down_forward(_dev(x, torch.float32, "x"), B, cin, ho, wo, ptr(packed3x3),
-                               ptr(packed1x1), out_channels,
+    rc = lib().dd_down_forward(_dev(x, torch.float32, "x"), B, cin, ho, wo, _ptr(packed3x3),
+                               _ptr(packed1x1), out_channels,
                                _opt(bias, torch.float32, "bias", out_channels), int(bool(relu)),
-                               ptr(st.buf) if st else None, ptr(y),
+                               _ptr(st.buf) if st else None, _ptr(y),
                                _opt(bias_sc, torch.float32, "bias_sc", out_channels),
-                               int(bool(relu_sc)), ptr(sts.buf) if sts else None, ptr(ys),
+                               int(bool(relu_sc)), _ptr(sts.buf) if sts else None, _ptr(ys),
                                gs, nst, *_head_operands(packed3x3, packed1x1), _stream(x))
     _check(rc, "dd_down_forward")
     # algorithmic bytes: x read once, y (and the shortcut output) written once
@@ -1703,36 +1670,21 @@ def conv_down_unit_input(y_prev: torch.Tensor, affine, packed3x3: torch.Tensor,
         raise ValueError("the unit form (residual) goes with the fused shortcut (packed1x1)")
     gs = int(group_size)
     G = -(-B // gs)
-    scale, shift = affine
-    for name, t in (("scale", scale), ("shift", shift)):
-        _dev(t, torch.float32, name)
-        if t.numel() != G * cin:
-            raise ValueError(f"{name} must have G*cin = {G * cin} entries")
-    if residual is not None:
-        _dev(residual, torch.float32, "residual")
-        if residual.shape != y_prev.shape:
-            raise ValueError("residual must match y_prev")
+    scale, shift = _affine_ptrs(affine, G, cin, ("scale", "shift"))
+    _residual_like(residual, y_prev)
     ho, wo = hi // 2, wi // 2
     shape = (B, out_channels, ho, wo)
     y = torch.empty(shape, dtype=torch.float32, device=y_prev.device)
     ys = torch.empty(shape, dtype=torch.float32, device=y_prev.device) \
         if packed1x1 is not None else None
-    nst = B if n_stat is None else min(max(int(n_stat), 0), B)
-    tiles = int(lib().dd_down_tiles_per_group(ho, wo, gs))
-    if tiles < 0:
-        raise DDError(f"no downsample tile geometry for {ho}x{wo} with group_size {gs}")
-    ipt = 4 if (ho, wo) == (4, 4) else 1
-    mk = lambda: BNStats(_stats_buffer(None, G, out_channels, tiles, y_prev.device), G, gs,  # noqa: E731
-                         nst, tiles, ipt, tiles // (gs // ipt), out_channels, ho * wo)
-    st = mk()
-    sts = mk() if ys is not None else None
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
+    nst = _n_stat(n_stat, B)
+    st, sts = _stats_head(ys is not None, G, gs, nst, out_channels, ho, wo, y_prev.device)
     e0 = _t0(y_prev)
     rc = lib().dd_down_forward_unit_input(
-        _dev(y_prev, torch.float32, "y_prev"), ptr(scale), ptr(shift), ptr(residual), B, cin,
-        ho, wo, ptr(packed3x3), ptr(packed1x1), out_channels, ptr(st.buf), ptr(y),
-        ptr(sts.buf) if sts else None, ptr(ys), gs, nst, *_head_operands(packed3x3, packed1x1),
-        _stream(y_prev))
+        _dev(y_prev, torch.float32, "y_prev"), scale, shift, _ptr(residual), B, cin, ho, wo,
+        _ptr(packed3x3), _ptr(packed1x1), out_channels, _ptr(st.buf), _ptr(y),
+        _ptr(sts.buf) if sts else None, _ptr(ys), gs, nst,
+        *_head_operands(packed3x3, packed1x1), _stream(y_prev))
     _check(rc, "dd_down_forward_unit_input")
     _t1(e0, "down_fwd_unit", 2.0 * B * ho * wo * cin * out_channels * (9 + (ys is not None)),
         y_prev, nbytes=4.0 * (B * cin * hi * wi * (1 + (residual is not None))
@@ -1770,19 +1722,17 @@ def down_backward(dh: torch.Tensor, packed3x3_t: torch.Tensor, in_channels: int,
             raise ValueError("dz must match dh")
     if mask_src is not None:
         _dev(mask_src, torch.float32, "mask_src", 4)
-        if tuple(mask_src.shape) != shape:
-            raise ValueError(f"mask_src must be {shape}")
+        _same_shape("mask_src", mask_src, shape)
     if mask_bits is not None:
         if mask_src is not None:
             raise ValueError("mask_src and mask_bits are exclusive")
         if mask_bits.dtype != torch.int32 or mask_bits.numel() * 32 != math.prod(shape):
             raise ValueError(f"mask_bits must be int32 [{math.prod(shape) // 32}]")
     dx = torch.empty(shape, dtype=torch.float32, device=dh.device)
-    ptr = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
     e0 = _t0(dh)
-    rc = lib().dd_down_backward(_dev(dh, torch.float32, "dh"), ptr(dz), B, cout, ho, wo,
-                                ptr(packed3x3_t), ptr(packed1x1_t), int(in_channels),
-                                ptr(mask_src), ptr(mask_bits), ptr(dx), _stream(dh))
+    rc = lib().dd_down_backward(_dev(dh, torch.float32, "dh"), _ptr(dz), B, cout, ho, wo,
+                                _ptr(packed3x3_t), _ptr(packed1x1_t), int(in_channels),
+                                _ptr(mask_src), _ptr(mask_bits), _ptr(dx), _stream(dh))
     _check(rc, "dd_down_backward")
     # algorithmic bytes: dh (and dz) read once, the mask read once (4 B or 1 bit per
     # element), dx written once

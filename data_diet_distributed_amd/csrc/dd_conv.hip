@@ -139,7 +139,7 @@ __global__ __launch_bounds__(256) void mask_plane_bits_kernel(
 static int dispatch(const Sel& s, int w, const Args& a, hipStream_t st) {
   const int k = s.rb * 1000 + s.e * 100 + s.na * 10 + s.wo;
   if (s.r2) return dispatch_r2(w, k, a, st);
-  if (w == 32 && k == 4000 + 100 + 10 + 2) return launch<32, 4, 1, 1, 2>(a, st);
+  if (w == 32 && k == 4000 + 100 + 10 + 2) return launch<kNarrow, 32, 4, 1, 1, 2>(a, st);
   return dispatch_small(w, k, a, st);
 }
 
@@ -349,7 +349,7 @@ int dd_conv3x3_unit_input_supported(int32_t h, int32_t w, int32_t cin, int32_t c
   if (h <= 0 || w <= 0 || cin <= conv::kStemCin || cout <= 0 || group_size <= 0 ||
       !conv::select(h, w, cout, group_size, &sl) || group_size % sl.e)
     return 0;
-  // the tiles with the specialised statistics epilogue (conv::launch / launch_r2)
+  // the tiles with the specialised statistics epilogue (conv::launch)
   const bool narrow = !sl.r2 && w == 32 && sl.rb == 4 && sl.e == 1 && sl.na == 1 && sl.wo == 2;
   const bool r2 = sl.r2 && sl.na == 1 && sl.wo == 4 && w >= 8;
   return (narrow || r2) && dd_conv3x3_tiles_per_group(h, w, group_size) > 0 ? 1 : 0;

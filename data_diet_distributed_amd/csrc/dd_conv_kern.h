@@ -1197,17 +1197,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_r2_kernel(const Args A) {
   }
 }
 
-// the dynamic-LDS attribute of one kernel instantiation, set once
-template <auto K>
-static void lds_attr(int bytes) {
-  static bool done = false;
-  if (!done) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-    done = true;
-  }
-}
-
 // the epilogue of a launch as an EPI code (kEpiSpec | operations)
 inline int epilogue_code(const Args& a) {
   return kEpiSpec | (a.bias ? kEpiBias : 0) | (a.residual ? kEpiRes : 0) |
@@ -1289,36 +1278,32 @@ static int dispatch_epi(const Args& a, Go& go) {
                : dispatch_epi_t<SPEC, Go, FUSE, 0>(a, go);
 }
 
+// the tile kernel of a launch: conv3x3_kernel, or conv3x3_r2_kernel (NA = 1 there)
+enum TileKind { kNarrow, kR2 };
+
 // epilogue specialisation where the scoring passes run (the 32x32 narrow tile and the r2
 // tiles); the other tile configs (channel counts the r2 tiles do not take) use the generic
 // epilogue
 template <int W, int RB, int E, int NA, int WO>
 constexpr bool kSpecNarrow = W == 32 && RB == 4 && E == 1 && NA == 1 && WO == 2;
 
-// launchers of one tile config for dispatch_epi
-template <int W, int RB, int E, int NA, int WO>
-struct GoNarrow {
+// the launcher of one tile config (kernel KIND, padded width PW) for dispatch_epi / stats_pick
+template <TileKind KIND, int W, int RB, int E, int NA, int WO, int PW>
+struct Go {
+  static constexpr int LDS = Cfg<W, RB, E, NA, WO>::LDS;
   const Args& a;
   dim3 g;
   hipStream_t st;
   template <int XF, bool KX1, int EPI>
-  int run() {
-    constexpr auto K = &conv3x3_kernel<W, RB, E, NA, WO, XF, KX1, EPI>;
-    lds_attr<K>(Cfg<W, RB, E, NA, WO>::LDS);
-    K<<<g, 256, Cfg<W, RB, E, NA, WO>::LDS, st>>>(a);
-    DD_CHECK_LAUNCH("dd_conv3x3_forward");
-    return DD_OK;
+  static constexpr auto kernel() {
+    if constexpr (KIND == kR2)
+      return &conv3x3_r2_kernel<W, RB, E, WO, XF, KX1, EPI, PW>;
+    else
+      return &conv3x3_kernel<W, RB, E, NA, WO, XF, KX1, EPI, PW>;
   }
-};
-template <int W, int RB, int E, int WO>
-struct GoR2 {
-  static constexpr int LDS = Cfg<W, RB, E, 1, WO>::LDS;
-  const Args& a;
-  dim3 g;
-  hipStream_t st;
   template <int XF, bool KX1, int EPI>
   int run() {
-    constexpr auto K = &conv3x3_r2_kernel<W, RB, E, WO, XF, KX1, EPI>;
+    constexpr auto K = kernel<XF, KX1, EPI>();
     lds_attr<K>(LDS);
     K<<<g, 256, LDS, st>>>(a);
     DD_CHECK_LAUNCH("dd_conv3x3_forward");
@@ -1326,123 +1311,75 @@ struct GoR2 {
   }
 };
 
-template <int W, int RB, int E, int NA, int WO>
+// the padded-width tiles' launch: the EL2N statistics epilogue, staged with the producer's BN
+// (+ ReLU) or raw, fp16 or bf16 operand halves.  (Not through dispatch_epi: that would name
+// padded-width kernels the kernels' static_assert forbids.)
+template <typename Go>
+static int stats_pick(const Args& a, Go& go) {
+  const bool xf = a.xf_mask != 0;
+  if (a.f16)
+    return xf ? go.template run<kXfAffine, false, kE_Stats | kEpiF16>()
+              : go.template run<kXfNone, false, kE_Stats | kEpiF16>();
+  return xf ? go.template run<kXfAffine, false, kE_Stats>()
+            : go.template run<kXfNone, false, kE_Stats>();
+}
+
+// n_tb / n_ob / n_tiles of a launch on tile config C.  PW (padded width: the map is a.wg wide,
+// narrower than the tile's W, and H need not fill the last row block) rounds n_tb up; the exact
+// tiles require H % RB == 0.
+template <typename C, int W, int RB, int E, int PW>
+static int plan_tiles(Args& a) {
+  if constexpr (!PW)
+    DD_REQUIRE(a.H % RB == 0, "dd_conv3x3_forward: H must be a multiple of the row block");
+  DD_REQUIRE(a.gsize % E == 0, "dd_conv3x3_forward: group_size %d must be a multiple of %d "
+             "(images per tile at %dx%d)", a.gsize, E, a.H, PW ? a.wg : W);
+  DD_REQUIRE(a.op % C::OB == 0, "dd_conv3x3_forward: padded outputs %d not a multiple of %d",
+             a.op, C::OB);
+  if constexpr (PW != 0) {
+    DD_REQUIRE(a.wg > 0 && a.wg <= W && (PW == 2 || a.wg % 4 == 0) && (E == 1 || a.H <= RB),
+               "dd_conv3x3_forward: no padded-width tile for %dx%d", a.H, a.wg);
+    DD_REQUIRE(epilogue_code(a) == kE_Stats && xf_mode(a) <= kXfAffine && !a.kx1,
+               "dd_conv3x3_forward: the padded-width tiles take the statistics epilogue only");
+  }
+  a.n_tb = PW ? (a.H + RB - 1) / RB : a.H / RB;
+  a.n_ob = a.op / C::OB;
+  const int64_t ntiles = ceil_div(a.B, E) * a.n_tb * a.n_ob;
+  DD_REQUIRE(ntiles < (1ll << 31), "dd_conv3x3_forward: too many tiles");
+  a.n_tiles = (int)ntiles;
+  return DD_OK;
+}
+
+// resident workgroups of a persistent launch (each walks tiles).  Wide tiles (NA == 2): one
+// workgroup per CU.  Narrow tiles: two per CU where the K loop is short and a tile's prologue
+// latency shows (measured +5-10 % at the stem, +3 % at 64 channels, -4 % at 512: one tile per
+// workgroup).  r2 tiles, padded or not: two per CU.  The padded-width narrow tile: as many as
+// its LDS image lets a CU hold (one at W = 64).
+template <TileKind KIND, int NA, int PW, int LDS>
+static int64_t resident_cap(int cin, int64_t ntiles) {
+  static_assert((KIND == kR2 ? 2 : 1) * LDS <= 160 * 1024,
+                "r2 tiles run two workgroups per CU");
+  if (KIND == kR2) return 2ll * device_cus();
+  if (PW) return (int64_t)(160 * 1024 / LDS) * device_cus();
+  if (NA == 2) return device_cus();
+  return cin <= 256 ? 2ll * device_cus() : ntiles;
+}
+
+// one launch of tile config <W, RB, E, NA, WO> on kernel KIND.  The r2 tiles (cout a multiple
+// of 128, one image row block per workgroup at 16x16, 2 images at 8x8, 8 at 4x4) get the
+// specialised epilogues, and the fused unit input at 16x16 and 8x8 (at 4x4 its residual
+// registers spill)
+template <TileKind KIND, int W, int RB, int E, int NA, int WO, int PW = 0>
 static int launch(Args a, hipStream_t st) {
-  using C = Cfg<W, RB, E, NA, WO>;
-  DD_REQUIRE(a.H % RB == 0, "dd_conv3x3_forward: H must be a multiple of the row block");
-  DD_REQUIRE(a.gsize % E == 0, "dd_conv3x3_forward: group_size %d must be a multiple of %d "
-             "(images per tile at %dx%d)", a.gsize, E, a.H, W);
-  DD_REQUIRE(a.op % C::OB == 0, "dd_conv3x3_forward: padded outputs %d not a multiple of %d",
-             a.op, C::OB);
-  a.n_tb = a.H / RB;
-  a.n_ob = a.op / C::OB;
-  const int64_t ntiles = ceil_div(a.B, E) * a.n_tb * a.n_ob;
-  DD_REQUIRE(ntiles < (1ll << 31), "dd_conv3x3_forward: too many tiles");
-  a.n_tiles = (int)ntiles;
-  // persistent: each resident workgroup walks tiles.  Wide tiles: one workgroup per CU.
-  // Narrow tiles: two per CU where the K loop is short and a tile's prologue latency shows
-  // (measured +5-10 % at the stem, +3 % at 64 channels, -4 % at 512: one tile per workgroup)
-  const int64_t cap = NA == 2 ? device_cus() : a.cin <= 256 ? 2ll * device_cus() : ntiles;
-  const int64_t grid = ntiles < cap ? ntiles : cap;
-  GoNarrow<W, RB, E, NA, WO> go{a, dim3((unsigned)grid), st};
-  return dispatch_epi<kSpecNarrow<W, RB, E, NA, WO>>(a, go);
-}
-
-template <int W, int RB, int E, int WO>
-static int launch_r2(Args a, hipStream_t st) {
-  using C = Cfg<W, RB, E, 1, WO>;
-  static_assert(2 * C::LDS <= 160 * 1024, "r2 tiles run two workgroups per CU");
-  DD_REQUIRE(a.H % RB == 0, "dd_conv3x3_forward: H must be a multiple of the row block");
-  DD_REQUIRE(a.gsize % E == 0, "dd_conv3x3_forward: group_size %d must be a multiple of %d "
-             "(images per tile at %dx%d)", a.gsize, E, a.H, W);
-  DD_REQUIRE(a.op % C::OB == 0, "dd_conv3x3_forward: padded outputs %d not a multiple of %d",
-             a.op, C::OB);
-  a.n_tb = a.H / RB;
-  a.n_ob = a.op / C::OB;
-  const int64_t ntiles = ceil_div(a.B, E) * a.n_tb * a.n_ob;
-  DD_REQUIRE(ntiles < (1ll << 31), "dd_conv3x3_forward: too many tiles");
-  a.n_tiles = (int)ntiles;
-  // persistent, two workgroups per CU
-  const int64_t cap = 2ll * device_cus();
-  GoR2<W, RB, E, WO> go{a, dim3((unsigned)(ntiles < cap ? ntiles : cap)), st};
-  // the r2 tiles (cout a multiple of 128, one image row block per workgroup at 16x16, 2 images
-  // at 8x8, 8 at 4x4) get the specialised epilogues, and the fused unit input at 16x16 and 8x8
-  // (at 4x4 its residual registers spill)
-  return dispatch_epi<true, decltype(go), W >= 8>(a, go);
-}
-
-// the padded-width r2 tiles (conv3x3_r2_kernel PW): the EL2N statistics launch, staged with the
-// producer's BN (+ ReLU) or raw, fp16 or bf16 operand halves; 128-output workgroups, two per CU
-template <int W, int RB, int E, int PW, int XF, int EPI>
-static int run_pw(const Args& a, dim3 g, hipStream_t st) {
-  constexpr auto K = &conv3x3_r2_kernel<W, RB, E, 4, XF, false, EPI, PW>;
-  lds_attr<K>(Cfg<W, RB, E, 1, 4>::LDS);
-  K<<<g, 256, Cfg<W, RB, E, 1, 4>::LDS, st>>>(a);
-  DD_CHECK_LAUNCH("dd_conv3x3_forward");
-  return DD_OK;
-}
-template <int W, int RB, int E, int PW>
-static int launch_r2_pw(Args a, hipStream_t st) {
-  using C = Cfg<W, RB, E, 1, 4>;
-  static_assert(2 * C::LDS <= 160 * 1024, "r2 tiles run two workgroups per CU");
-  DD_REQUIRE(a.gsize % E == 0, "dd_conv3x3_forward: group_size %d must be a multiple of %d "
-             "(images per tile at %dx%d)", a.gsize, E, a.H, a.wg);
-  DD_REQUIRE(a.op % C::OB == 0, "dd_conv3x3_forward: padded outputs %d not a multiple of %d",
-             a.op, C::OB);
-  DD_REQUIRE(a.wg > 0 && a.wg <= W && (PW == 2 || a.wg % 4 == 0) && (E == 1 || a.H <= RB),
-             "dd_conv3x3_forward: no padded-width tile for %dx%d", a.H, a.wg);
-  DD_REQUIRE(epilogue_code(a) == kE_Stats && xf_mode(a) <= kXfAffine && !a.kx1,
-             "dd_conv3x3_forward: the padded-width tiles take the statistics epilogue only");
-  a.n_tb = (a.H + RB - 1) / RB;
-  a.n_ob = a.op / C::OB;
-  const int64_t ntiles = ceil_div(a.B, E) * a.n_tb * a.n_ob;
-  DD_REQUIRE(ntiles < (1ll << 31), "dd_conv3x3_forward: too many tiles");
-  a.n_tiles = (int)ntiles;
-  const int64_t cap = 2ll * device_cus();
-  const dim3 g((unsigned)(ntiles < cap ? ntiles : cap));
-  const bool xf = a.xf_mask != 0;
-  if (a.f16)
-    return xf ? run_pw<W, RB, E, PW, kXfAffine, kE_Stats | kEpiF16>(a, g, st)
-              : run_pw<W, RB, E, PW, kXfNone, kE_Stats | kEpiF16>(a, g, st);
-  return xf ? run_pw<W, RB, E, PW, kXfAffine, kE_Stats>(a, g, st)
-            : run_pw<W, RB, E, PW, kXfNone, kE_Stats>(a, g, st);
-}
-
-// the padded-width narrow tile (conv3x3_kernel PW: 64-output workgroups, the EL2N statistics
-// launch); its LDS image takes one workgroup per CU at W = 64
-template <int W, int RB, int E, int PW, int XF, int EPI>
-static int run_pw_narrow(const Args& a, dim3 g, hipStream_t st) {
-  constexpr auto K = &conv3x3_kernel<W, RB, E, 1, 2, XF, false, EPI, PW>;
-  lds_attr<K>(Cfg<W, RB, E, 1, 2>::LDS);
-  K<<<g, 256, Cfg<W, RB, E, 1, 2>::LDS, st>>>(a);
-  DD_CHECK_LAUNCH("dd_conv3x3_forward");
-  return DD_OK;
-}
-template <int W, int RB, int E, int PW>
-static int launch_narrow_pw(Args a, hipStream_t st) {
-  using C = Cfg<W, RB, E, 1, 2>;
-  static_assert(C::LDS <= 160 * 1024, "LDS");
-  DD_REQUIRE(a.gsize % E == 0, "dd_conv3x3_forward: group_size %d must be a multiple of %d "
-             "(images per tile at %dx%d)", a.gsize, E, a.H, a.wg);
-  DD_REQUIRE(a.op % C::OB == 0, "dd_conv3x3_forward: padded outputs %d not a multiple of %d",
-             a.op, C::OB);
-  DD_REQUIRE(a.wg > 0 && a.wg <= W && (PW == 2 || a.wg % 4 == 0) && (E == 1 || a.H <= RB),
-             "dd_conv3x3_forward: no padded-width tile for %dx%d", a.H, a.wg);
-  DD_REQUIRE(epilogue_code(a) == kE_Stats && xf_mode(a) <= kXfAffine && !a.kx1,
-             "dd_conv3x3_forward: the padded-width tiles take the statistics epilogue only");
-  a.n_tb = (a.H + RB - 1) / RB;
-  a.n_ob = a.op / C::OB;
-  const int64_t ntiles = ceil_div(a.B, E) * a.n_tb * a.n_ob;
-  DD_REQUIRE(ntiles < (1ll << 31), "dd_conv3x3_forward: too many tiles");
-  a.n_tiles = (int)ntiles;
-  const int64_t cap = (int64_t)(160 * 1024 / C::LDS) * device_cus();
-  const dim3 g((unsigned)(ntiles < cap ? ntiles : cap));
-  const bool xf = a.xf_mask != 0;
-  if (a.f16)
-    return xf ? run_pw_narrow<W, RB, E, PW, kXfAffine, kE_Stats | kEpiF16>(a, g, st)
-              : run_pw_narrow<W, RB, E, PW, kXfNone, kE_Stats | kEpiF16>(a, g, st);
-  return xf ? run_pw_narrow<W, RB, E, PW, kXfAffine, kE_Stats>(a, g, st)
-            : run_pw_narrow<W, RB, E, PW, kXfNone, kE_Stats>(a, g, st);
+  using G = Go<KIND, W, RB, E, NA, WO, PW>;
+  if (const int rc = plan_tiles<Cfg<W, RB, E, NA, WO>, W, RB, E, PW>(a)) return rc;
+  const int64_t cap = resident_cap<KIND, NA, PW, G::LDS>(a.cin, a.n_tiles);
+  G go{a, dim3((unsigned)(a.n_tiles < cap ? a.n_tiles : cap)), st};
+  if constexpr (PW != 0)
+    return stats_pick(a, go);
+  else if constexpr (KIND == kR2)
+    return dispatch_epi<true, G, W >= 8>(a, go);
+  else
+    return dispatch_epi<kSpecNarrow<W, RB, E, NA, WO>>(a, go);
 }
 
 // tile-config dispatchers of the other translation units (key = rb*1000 + e*100 + na*10 + wo)

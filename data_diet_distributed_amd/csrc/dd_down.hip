@@ -1120,16 +1120,8 @@ __global__ void pack1x1_kernel(const float* __restrict__ w, int cout, int cin, i
 template <int WO, int RB, int E, bool SC, int WA, int EPI = 0, int XM = 0, bool F16 = false>
 static int launch_fwd(FwdArgs a, hipStream_t st) {
   using C = DCfg<WO, RB, E>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&down_fwd_kernel<WO, RB, E, SC, false, WA, EPI, XM, F16>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    (void)hipFuncSetAttribute(
-        reinterpret_cast<const void*>(&down_fwd_kernel<WO, RB, E, SC, true, WA, EPI, XM, F16>),
-        hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    attr = true;
-  }
+  constexpr auto K = &down_fwd_kernel<WO, RB, E, SC, false, WA, EPI, XM, F16>;
+  constexpr auto KP = &down_fwd_kernel<WO, RB, E, SC, true, WA, EPI, XM, F16>;  // persistent
   DD_REQUIRE(a.HO % RB == 0, "dd_down_forward: HO must be a multiple of the row block");
   DD_REQUIRE(a.gsize % E == 0, "dd_down_forward: group_size %d must be a multiple of %d",
              a.gsize, E);
@@ -1146,12 +1138,13 @@ static int launch_fwd(FwdArgs a, hipStream_t st) {
   const bool pt = a.cin <= 64;
   const int64_t cap = pt ? 2ll * device_cus() : ntiles;
   const int64_t grid = ntiles < cap ? ntiles : cap;
-  if (pt)
-    down_fwd_kernel<WO, RB, E, SC, true, WA, EPI, XM, F16>
-        <<<(unsigned)grid, 256, C::LDS, st>>>(a);
-  else
-    down_fwd_kernel<WO, RB, E, SC, false, WA, EPI, XM, F16>
-        <<<(unsigned)grid, 256, C::LDS, st>>>(a);
+  if (pt) {
+    lds_attr<KP>(C::LDS);
+    KP<<<(unsigned)grid, 256, C::LDS, st>>>(a);
+  } else {
+    lds_attr<K>(C::LDS);
+    K<<<(unsigned)grid, 256, C::LDS, st>>>(a);
+  }
   DD_CHECK_LAUNCH("dd_down_forward");
   return DD_OK;
 }
@@ -1162,18 +1155,13 @@ template <int WO, int RB, int PW, int XM, bool F16>
 static int launch_fwd_pw(FwdArgs a, hipStream_t st) {
   using C = DCfg<WO, RB, 1>;
   constexpr auto K = &down_fwd_kernel<WO, RB, 1, false, false, 4, 0, XM, F16, PW>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    attr = true;
-  }
   a.n_tb = (a.HO + RB - 1) / RB;
   a.n_ob = (int)ceil_div(a.cout, 128);
   a.tiles_per_group = a.gsize * a.n_tb * 2;  // two 32-position partials per tile
   const int64_t ntiles = a.B * a.n_tb * a.n_ob;
   DD_REQUIRE(ntiles < (1ll << 31), "dd_down_forward: too many tiles");
   a.n_tiles = (int)ntiles;
+  lds_attr<K>(C::LDS);
   K<<<(unsigned)ntiles, 256, C::LDS, st>>>(a);
   DD_CHECK_LAUNCH("dd_down_forward");
   return DD_OK;
@@ -1203,41 +1191,18 @@ static int fwd_wa(int cout) {
   return f == 4 && conv::pad_to(cout, 64) % 128 == 0 ? 4 : 2;
 }
 
-template <int WO, int RB, int E, bool SC>
-static int launch_bwd(BwdArgs a, hipStream_t st) {
-  using C = UCfg<WO, RB, E, SC>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&down_bwd_kernel<WO, RB, E, SC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    attr = true;
-  }
-  DD_REQUIRE(a.HO % RB == 0, "dd_down_backward: HO must be a multiple of the row block");
-  a.n_tb = a.HO / RB;
+// one backward launch of kernel K (down_bwd_kernel, or down_bwd2_kernel with PER_CU = 2: its
+// 128-position workgroups run two per CU) on row blocks of rb rows, e images per tile
+template <auto K, int LDS, int PER_CU>
+static int launch_bwd(BwdArgs a, int rb, int e, hipStream_t st) {
+  static_assert(PER_CU * LDS <= 160 * 1024, "two workgroups per CU");
+  DD_REQUIRE(a.HO % rb == 0, "dd_down_backward: HO must be a multiple of the row block");
+  a.n_tb = a.HO / rb;
   a.n_ob = (int)ceil_div(a.cin, 64);
-  const int64_t grid = ceil_div(a.B, E) * a.n_tb * a.n_ob;
+  const int64_t grid = ceil_div(a.B, e) * a.n_tb * a.n_ob;
   DD_REQUIRE(grid < (1ll << 31), "dd_down_backward: grid too large");
-  down_bwd_kernel<WO, RB, E, SC><<<(unsigned)grid, 256, C::LDS, st>>>(a);
-  DD_CHECK_LAUNCH("dd_down_backward");
-  return DD_OK;
-}
-
-template <int WO, int RB, int E, bool SC>
-static int launch_bwd2(BwdArgs a, hipStream_t st) {
-  using C = UCfg<WO, RB, E, SC>;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&down_bwd2_kernel<WO, RB, E, SC>),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS);
-    attr = true;
-  }
-  static_assert(2 * C::LDS <= 160 * 1024, "two workgroups per CU");
-  DD_REQUIRE(a.HO % RB == 0, "dd_down_backward: HO must be a multiple of the row block");
-  a.n_tb = a.HO / RB;
-  a.n_ob = (int)ceil_div(a.cin, 64);
-  const int64_t grid = ceil_div(a.B, E) * a.n_tb * a.n_ob;
-  DD_REQUIRE(grid < (1ll << 31), "dd_down_backward: grid too large");
-  down_bwd2_kernel<WO, RB, E, SC><<<(unsigned)grid, 256, C::LDS, st>>>(a);
+  lds_attr<K>(LDS);
+  K<<<(unsigned)grid, 256, LDS, st>>>(a);
   DD_CHECK_LAUNCH("dd_down_backward");
   return DD_OK;
 }
@@ -1530,28 +1495,26 @@ int dd_down_backward(const float* dh, const float* dz, int64_t B, int32_t cout, 
   a.xcd = xcd;
   hipStream_t st = as_stream(stream);
   const bool sc = dz != nullptr;
-#define DD_UP2(WO_, RB_, E_)                                      \
-  return sc ? down::launch_bwd2<WO_, RB_, E_, true>(a, st)        \
-            : down::launch_bwd2<WO_, RB_, E_, false>(a, st)
+#define DD_UP(KERN, PER_CU, WO_, RB_, E_)                                                  \
+  return sc ? down::launch_bwd<&down::KERN<WO_, RB_, E_, true>,                             \
+                               down::UCfg<WO_, RB_, E_, true>::LDS, PER_CU>(a, RB_, E_, st) \
+            : down::launch_bwd<&down::KERN<WO_, RB_, E_, false>,                            \
+                               down::UCfg<WO_, RB_, E_, false>::LDS, PER_CU>(a, RB_, E_, st)
   // mask_bits is read only by the 128-position kernel: exactly its three dispatch cases below
-  // (a 16-wide map with ho % 8 != 0 falls through to launch_bwd, which reads A.mask only)
+  // (a 16-wide map with ho % 8 != 0 falls through to down_bwd_kernel, which reads A.mask only)
   DD_REQUIRE(!mask_bits || (down::bwd2() && ((wo == 16 && ho % 8 == 0) || (wo == 8 && ho == 8) ||
                                              (wo == 4 && ho == 4))),
              "dd_down_backward: mask_bits needs the 128-position kernel (16-wide maps with "
              "ho %% 8 == 0, 8x8, 4x4)");
   if (down::bwd2()) {
-    if (wo == 16 && ho % 8 == 0) DD_UP2(16, 8, 1);
-    if (wo == 8 && ho == 8) DD_UP2(8, 8, 2);
-    if (wo == 4 && ho == 4) DD_UP2(4, 4, 8);
+    if (wo == 16 && ho % 8 == 0) DD_UP(down_bwd2_kernel, 2, 16, 8, 1);
+    if (wo == 8 && ho == 8) DD_UP(down_bwd2_kernel, 2, 8, 8, 2);
+    if (wo == 4 && ho == 4) DD_UP(down_bwd2_kernel, 2, 4, 4, 8);
   }
-#undef DD_UP2
-#define DD_UP(WO_, RB_, E_)                                       \
-  return sc ? down::launch_bwd<WO_, RB_, E_, true>(a, st)         \
-            : down::launch_bwd<WO_, RB_, E_, false>(a, st)
-  if (wo == 32) DD_UP(32, 2, 1);
-  if (wo == 16) DD_UP(16, 4, 1);
-  if (wo == 8) DD_UP(8, 8, 1);
-  DD_UP(4, 4, 4);
+  if (wo == 32) DD_UP(down_bwd_kernel, 1, 32, 2, 1);
+  if (wo == 16) DD_UP(down_bwd_kernel, 1, 16, 4, 1);
+  if (wo == 8) DD_UP(down_bwd_kernel, 1, 8, 8, 1);
+  DD_UP(down_bwd_kernel, 1, 4, 4, 4);
 #undef DD_UP
 }
 

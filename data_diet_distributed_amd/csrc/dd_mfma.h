@@ -57,6 +57,16 @@ __device__ __forceinline__ void static_for(F&& f) {
   static_for_impl(f, std::make_integer_sequence<int, N>{});
 }
 
+// the dynamic-LDS attribute of one kernel instantiation, set once
+template <auto K>
+static void lds_attr(int bytes) {
+  static bool done = false;
+  if (!done) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(K),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    done = true;
+  }
+}
 
 __host__ __device__ constexpr int pad_to(int v, int m) { return (v + m - 1) / m * m; }
 

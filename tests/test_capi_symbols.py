@@ -23,6 +23,50 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(lib, name), name
 
 
+def _ctype(c_type: str, ret: bool = False):
+    """The ctypes type the binding must declare for one C parameter / return type."""
+    import ctypes
+    t = " ".join(c_type.replace("*", " * ").split())
+    if t.endswith("*"):
+        if t == "const dd_conv_geom *":
+            return ctypes.POINTER(_capi.ConvGeom)
+        if ret and t == "const char *":
+            return ctypes.c_char_p
+        return ctypes.c_void_p
+    return {"int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+            "uint64_t": ctypes.c_uint64, "size_t": ctypes.c_size_t, "float": ctypes.c_float,
+            "double": ctypes.c_double}[t]
+
+
+def declared_signatures():
+    """{name: (restype, [argtypes])} of every function include/dd_capi.h declares."""
+    src = open(os.path.join(ROOT, "include", "dd_capi.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*|^\s*#[^\n]*", "", src, flags=re.M)
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \t*]*?)\s*\b(dd_[a-z0-9_]+)\s*\(([^)]*)\)\s*;",
+                                        src):
+        params = [p.strip() for p in params.split(",")]
+        if params == ["void"]:
+            params = []
+        # drop the parameter name: the last identifier of "type name"
+        args = [_ctype(re.sub(r"\b[A-Za-z_]\w*$", "", p)) for p in params]
+        out[name] = (_ctype(ret, ret=True), args)
+    return out
+
+
+def test_binding_signatures_match_the_header():
+    """restype and argtypes of every bound function equal the header's declaration: a swapped
+    or mistyped argument in the hand-written table would pass wrong values without an error."""
+    sigs = declared_signatures()
+    assert sorted(sigs) == declared_symbols()
+    lib = _capi.lib()
+    for name, (res, args) in sigs.items():
+        fn = getattr(lib, name)
+        assert fn.restype == res, (name, fn.restype, res)
+        assert list(fn.argtypes) == args, (name, fn.argtypes, args)
+
+
 def test_host_only_entry_points():
     # no device work: ABI version, keep-count, workspace queries, method planning
     assert _capi.lib().dd_abi_version() == 10
