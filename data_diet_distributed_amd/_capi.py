@@ -50,6 +50,7 @@ EXPORTS = (
     "dd_nn_workspace_bytes", "dd_nn_same_class",
     "dd_knn_workspace_bytes", "dd_knn",
     "dd_kcenter_workspace_bytes", "dd_kcenter_seed_batch", "dd_kcenter_greedy",
+    "dd_kmeans_workspace_bytes", "dd_kmeans_assign", "dd_kmeans_centroids",
 )
 
 
@@ -111,6 +112,10 @@ def lib():
                 "dd_kcenter_seed_batch": (I32, [I32, I32]),
                 "dd_kcenter_greedy": (I32, [P, P, I64, I32, P, I32, P, P, I64, P, I64, I32, I32,
                                             P, P, P, P, P, SZ, P]),
+                "dd_kmeans_workspace_bytes": (SZ, [I64, I32, I32, I32]),
+                "dd_kmeans_assign": (I32, [P, I64, P, I32, I32, I32, I32, P, P, P, P, P, P, P,
+                                           SZ, P]),
+                "dd_kmeans_centroids": (I32, [P, P, I32, I32, P, P]),
                 "dd_conv_pegrad_method": (I32, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_workspace_bytes": (SZ, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_sqnorm": (I32, [P, P, ctypes.POINTER(ConvGeom), P, I32, I32, P,
@@ -762,6 +767,81 @@ def check_kcenter(stat):
     if bad_rows:
         raise ValueError(f"kcenter: {bad_rows} feature row(s) with a NaN or infinite element: the "
                          f"coverage keep-set is undefined")
+
+
+# ---- distance to the nearest k-means centroid ---------------------------------------------------
+KMEANS_MAX_K = 4096            # DD_KMEANS_MAX_K
+KMEANS_MAX_N = 1 << 24         # rows one cluster's int64 fixed-point sums hold without overflow
+
+
+def kmeans_workspace_bytes(n: int, k: int, D: int, operands: str = "f16x3") -> int:
+    """Bytes of kmeans_assign's workspace (dd_kmeans_workspace_bytes; 0 for sizes outside the
+    entry point's limits)."""
+    return int(lib().dd_kmeans_workspace_bytes(int(n), int(k), int(D), OPERANDS[operands]))
+
+
+def kmeans_assign(rows: torch.Tensor, centroids: torch.Tensor, *, operands: str = "f16x3",
+                  repack_rows: bool = True, sums=None, counts=None, bad=None, assign=None,
+                  dist=None, accum=None, workspace=None):
+    """One Lloyd assignment of rows [n, D] to centroids [Kc, D] (dd_kmeans_assign): per row the
+    centroid with the smallest (key, cluster id).  Writes whichever are given of assign int32 [n]
+    and dist fp32 [n] (-1 / NaN for a row with a NaN, an infinity or |v| >= 2^15), accumulates
+    into accum fp32 [n] (+= the distance) and into sums int64 [Kc, D] / counts int64 [Kc] (both or
+    neither: the exact 2^-24 fixed-point sums and the sizes of the clusters; the caller clears
+    them) and bad int64 [1] (the unrepresentable rows; None: a zeroed one is made).
+    repack_rows=False reuses the operand halves of the rows that an earlier call with the same
+    rows and sizes left in `workspace`.  workspace: a uint8 tensor of kmeans_workspace_bytes, or
+    None to allocate one.  Returns (workspace, bad)."""
+    _dev(rows, torch.float32, "rows", 2)
+    _dev(centroids, torch.float32, "centroids", 2)
+    n, D = rows.shape
+    Kc = centroids.shape[0]
+    if centroids.shape[1] != D:
+        raise ValueError(f"centroids must be [Kc, {D}] (got {tuple(centroids.shape)})")
+    if not 1 <= Kc <= KMEANS_MAX_K:
+        raise ValueError(f"kmeans_assign: Kc must be in 1..{KMEANS_MAX_K} (got {Kc})")
+    if (sums is None) != (counts is None):
+        raise ValueError("kmeans_assign: sums and counts go together")
+    if sums is None and assign is None and dist is None and accum is None:
+        raise ValueError("kmeans_assign: no output requested")
+    code = _operands_code(operands)
+    need = int(lib().dd_kmeans_workspace_bytes(n, Kc, D, code))
+    if need == 0:
+        raise ValueError(f"kmeans_assign: unsupported size n={n}, Kc={Kc}, D={D}")
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        if not repack_rows:
+            raise ValueError("kmeans_assign: repack_rows=False needs the earlier call's workspace")
+        workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int64, device=rows.device)
+    ptrs = [_opt(sums, torch.int64, "sums", Kc * D), _opt(counts, torch.int64, "counts", Kc),
+            _dev(bad, torch.int64, "bad"), _opt(assign, torch.int32, "assign", n),
+            _opt(dist, torch.float32, "dist", n), _opt(accum, torch.float32, "accum", n)]
+    if n == 0:  # nothing to do (and an empty tensor's pointer is NULL: "not requested")
+        return workspace, bad
+    Dp = (D + 15) // 16 * 16
+    e0 = _t0(rows, always=True)
+    rc = lib().dd_kmeans_assign(
+        _dev(rows, torch.float32, "rows"), n, _dev(centroids, torch.float32, "centroids"), Kc, D,
+        code, int(bool(repack_rows)), *ptrs, _dev(workspace, torch.uint8, "workspace"),
+        workspace.numel() * workspace.element_size(), _stream(rows))
+    _check(rc, "dd_kmeans_assign")
+    # the fp32 rows read once (and once more by the pack), the halves written once and read once
+    _t1(e0, "el2n", n * (4.0 * D + 4.0 * Dp + (8.0 * D + 4.0 * Dp if repack_rows else 0.0)), rows)
+    return workspace, bad
+
+
+def kmeans_centroids(sums: torch.Tensor, counts: torch.Tensor, centroids: torch.Tensor):
+    """centroids[j] = sums[j] / counts[j] * 2^-24 in place where counts[j] > 0; an empty cluster
+    keeps its centroid (dd_kmeans_centroids)."""
+    _dev(centroids, torch.float32, "centroids", 2)
+    Kc, D = centroids.shape
+    rc = lib().dd_kmeans_centroids(_opt(sums, torch.int64, "sums", Kc * D),
+                                   _opt(counts, torch.int64, "counts", Kc), Kc, D,
+                                   _dev(centroids, torch.float32, "centroids"),
+                                   _stream(centroids))
+    _check(rc, "dd_kmeans_centroids")
+    return centroids
 
 
 def label_counter(device) -> torch.Tensor:

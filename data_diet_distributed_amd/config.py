@@ -19,10 +19,14 @@ DEFAULTS = {
     # to the class prototype in feature space, scoring.FEATURE_METHODS) | nn (the distance to
     # the nearest other example of the same class, scoring.NEIGHBOR_METHODS) | knn, knn_disagree
     # (the mean distance to the knn_k nearest other examples of any class and the share of them
-    # with another label, scoring.KNN_METHODS); select_by takes any
+    # with another label, scoring.KNN_METHODS) | kmeans (the distance to the nearest centroid of
+    # a k-means clustering of the feature rows: the prototype distance without labels,
+    # scoring.CLUSTER_METHODS); select_by takes any
     "score_methods": ["el2n"],
     "select_by": "el2n",
     "knn_k": 5,                       # neighbours of knn / knn_disagree (1..16)
+    "kmeans_k": 0,                    # clusters of kmeans (0: num_classes; at most 4096)
+    "kmeans_iters": 20,               # Lloyd updates of kmeans per checkpoint (1..1000)
     "select_policy": "global",        # global (reference) | stratified | balanced class quotas
     "select_skip": 0,                 # ranks skipped from the top before the k kept ones
     "select_fill": "score",           # score (the rank cut) | kcenter (coverage: greedy k-center)

@@ -1,14 +1,15 @@
 """The consumers of the EL2N pass's train-BN forward: LogitScores (el2n + LOGIT_METHODS, from
-each launch's logits), ProtoScore, NNScore and KNNScore (from the checkpoint's pooled feature
-rows, over every rank), and ForwardScores, which holds the requested ones for one score_shard
-call.
+each launch's logits), ProtoScore, KMeansScore, NNScore and KNNScore (from the checkpoint's pooled
+feature rows, over every rank), and ForwardScores, which holds the requested ones for one
+score_shard call.
 
 The pass hands every launch's logits to `consume` and, when `features` is not None, writes the
 launch's feature rows there; after a checkpoint's last chunk it calls `end_checkpoint`.  Every
 rank issues its collectives in the same order: the counts all-reduce (proto) and the lengths and
-labels all-gathers (nn and the knn scores: one of each, shared, GatheredRows) at construction,
-then per checkpoint the proto all-reduce followed by the one all-gather of the feature rows that
-nn and the knn scores share.
+labels all-gathers (nn and the knn scores: one of each, shared, GatheredRows; kmeans alone takes
+the lengths only) at construction, then per checkpoint the proto all-reduce, the kmeans
+all-reduces (the seed rows, then one per Lloyd iteration) and last the one all-gather of the
+feature rows that nn and the knn scores share.
 """
 from __future__ import annotations
 
@@ -96,6 +97,67 @@ def nearest_k(features: torch.Tensor, labels: torch.Tensor, num_classes: int, k:
     _capi.knn(features, ids, features, ids, k, q_label=labels, c_label=labels, operands=operands,
               mean_dist=mean, disagree=share)
     return mean, share
+
+
+def kmeans_seed_rows(N: int, k: int) -> List[int]:
+    """The dataset rows the k centroids start from: s_j = floor((2 j + 1) N / (2 k)), evenly
+    spaced, distinct for N >= k, and a function of N and k alone."""
+    return [((2 * j + 1) * N) // (2 * k) for j in range(k)]
+
+
+def check_kmeans_size(N: int, k: int):
+    """k-means needs a seed row per cluster, and its fixed-point sums (|q| < 2^39 per element,
+    int64) hold fewer than 2^24 rows in one cluster: reject a dataset outside k <= N < 2^24."""
+    if N < k:
+        raise ValueError(f"kmeans_k={k} needs at least {k} examples in the whole dataset (got "
+                         f"{N}): every cluster starts from a row of its own")
+    if N >= _capi.KMEANS_MAX_N:
+        raise ValueError(f"kmeans: {N} examples; the exact int64 feature sums hold fewer than "
+                         f"{_capi.KMEANS_MAX_N} (2^24) rows in one cluster")
+
+
+def lloyd_step(features, centroids, reduce, workspace, operands, repack, group=None, world=1):
+    """One Lloyd update of `centroids` [k, D] in place from this rank's rows `features`: the
+    int64 buffer `reduce` [k D + k + 1] (the sums, the counts, the unrepresentable rows) is
+    cleared, filled by one dd_kmeans_assign launch, summed over `group`'s `world` ranks (an exact
+    integer all-reduce) and turned into the centroids.  Returns the workspace."""
+    k, D = centroids.shape
+    reduce.zero_()
+    workspace, _ = _capi.kmeans_assign(
+        features, centroids, operands=operands, repack_rows=repack,
+        sums=reduce[:k * D].view(k, D), counts=reduce[k * D:k * D + k], bad=reduce[k * D + k:],
+        workspace=workspace)
+    if world > 1:
+        _all_reduce_sum(reduce, group)
+    _capi.kmeans_centroids(reduce[:k * D].view(k, D), reduce[k * D:k * D + k], centroids)
+    return workspace
+
+
+def kmeans(features: torch.Tensor, k: int, iters: int, operands: str = "f16x3"):
+    """(centroids fp32 [k, D], assign int32 [n], dist fp32 [n]): `iters` Lloyd updates over the rows
+    of `features` [n, D] from the seed rows kmeans_seed_rows(n, k), then each row's nearest
+    centroid (a tie goes to the smaller cluster id) and its distance to it (include/dd_capi.h
+    dd_kmeans_assign).  Raises ValueError for n < k and, after one read of the kernel's counter,
+    for a row with a NaN, an infinity or |v| >= 2^15 (its distance would be NaN)."""
+    n, D = features.shape
+    k, iters = int(k), int(iters)
+    _check_width("kmeans", D)
+    check_kmeans_size(n, k)
+    dev = features.device
+    seeds = torch.tensor(kmeans_seed_rows(n, k), dtype=torch.int64).to(dev)
+    centroids = features.index_select(0, seeds).contiguous()
+    reduce = torch.empty(k * D + k + 1, dtype=torch.int64, device=dev)
+    ws = None
+    for it in range(iters):
+        ws = lloyd_step(features, centroids, reduce, ws, operands, it == 0)
+    assign = torch.empty(n, dtype=torch.int32, device=dev)
+    dist = torch.empty(n, dtype=torch.float32, device=dev)
+    _, bad = _capi.kmeans_assign(features, centroids, operands=operands, repack_rows=ws is None,
+                                 assign=assign, dist=dist, workspace=ws)
+    if int(bad.item()):
+        raise ValueError(f"kmeans: {int(bad.item())} feature row(s) with a NaN, an infinite or an "
+                         f"|v| >= 2^15 element: their distance is undefined")
+    return centroids, assign, dist
 
 
 def ensemble_mean(acc: torch.Tensor, K: int) -> torch.Tensor:
@@ -189,6 +251,57 @@ class ProtoScore:
 
     def finalize(self, K: int) -> Dict[str, torch.Tensor]:
         return {"proto": ensemble_mean(self.accum, K)}
+
+
+class KMeansScore:
+    """The per-call state of the kmeans score for the shard's `labels` [n] (read only for `bad`,
+    this shard's count of labels outside [0, C): the clustering takes no labels), built once and
+    reused by every checkpoint: the seed rows this rank owns among kmeans_seed_rows of the whole
+    dataset (`lengths` / `rank`: the shard lengths, GatheredRows' where nn or the knn scores hold
+    them), the centroids [k, D], the int64 buffer [k D + k + 1] that is all-reduced per Lloyd
+    iteration (sums, counts, unrepresentable rows), the accumulator and the kernel's workspace
+    (4 (n + k) pad16(D) bytes).  A dataset outside k <= N < 2^24 is rejected."""
+
+    def __init__(self, labels: torch.Tensor, linear, group, lengths, rank: int, operands: str,
+                 k: int, iters: int):
+        n, dev = labels.numel(), labels.device
+        C, D = linear.out_features, linear.in_features
+        _check_width("kmeans", D)
+        self.k, self.iters = int(k) or C, int(iters)  # (kmeans_k = 0: the class count)
+        N, offset = sum(lengths), sum(lengths[:rank])
+        check_kmeans_size(N, self.k)
+        self.group, self.world, self.operands = group, len(lengths), operands
+        _, self.bad = _capi.class_counts(labels.contiguous(), C, check=False)
+        mine = [(j, s - offset) for j, s in enumerate(kmeans_seed_rows(N, self.k))
+                if offset <= s < offset + n]
+        self.seed_j, self.seed_row = (torch.tensor([m[i] for m in mine], dtype=torch.int64).to(dev)
+                                      for i in (0, 1))
+        self.centroids = torch.empty((self.k, D), dtype=torch.float32, device=dev)
+        self.reduce = torch.empty(self.k * D + self.k + 1, dtype=torch.int64, device=dev)
+        self.accum = torch.zeros(n, dtype=torch.float32, device=dev)
+        need = _capi.kmeans_workspace_bytes(n, self.k, D, operands)
+        self.workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+
+    def end_checkpoint(self, features: torch.Tensor):
+        """At the same point of a checkpoint as ProtoScore's, on the current stream, nothing read
+        back: the seed rows (each rank writes those it owns into zeros; the int32 view is summed,
+        so that adding zeros changes no bit), `iters` Lloyd updates (the rows' operand halves are
+        made by the first), and the scoring assignment."""
+        self.centroids.zero_()
+        self.centroids.index_copy_(0, self.seed_j, features.index_select(0, self.seed_row))
+        if self.world > 1:
+            _all_reduce_sum(self.centroids.view(torch.int32), self.group)
+        for it in range(self.iters):
+            self.workspace = lloyd_step(features, self.centroids, self.reduce, self.workspace,
+                                        self.operands, it == 0, self.group, self.world)
+        _capi.kmeans_assign(features, self.centroids, operands=self.operands, repack_rows=False,
+                            accum=self.accum, bad=self.reduce[-1:], workspace=self.workspace)
+
+    def finalize(self, K: int) -> Dict[str, torch.Tensor]:
+        """(`reduce[-1]` holds the last assignment's count of unrepresentable rows over every rank
+        for a caller that wants to name them; the engine reads nothing back here: such a row's
+        score is NaN, which ScoringEngine._validate rejects or re-scores on bf16 halves.)"""
+        return {"kmeans": ensemble_mean(self.accum, K)}
 
 
 class GatheredRows:
@@ -308,7 +421,7 @@ class ForwardScores:
         self.kcenter_ckpt, self.kcenter_rows, self._ckpts_done = kcenter_ckpt, None, 0
         logit = [m for m in methods if m in LOGIT_FAMILY]
         self.logit = LogitScores(logit, n, labels.device) if logit else None
-        self.proto = self.nn = self.knn = self.rows = None
+        self.proto = self.kmeans = self.nn = self.knn = self.rows = None
         if "proto" in methods:
             self.proto = ProtoScore(labels, linear, group, cfg.batch_size)
         knn = [m for m in methods if m in KNN_METHODS]
@@ -319,10 +432,15 @@ class ForwardScores:
             self.nn = NNScore(labels, linear, self.rows, cfg.el2n_operands)
         if knn:
             self.knn = KNNScore(knn, labels, linear, self.rows, cfg.el2n_operands, cfg.knn_k)
+        if "kmeans" in methods:
+            lengths, rank = ((self.rows.lengths, self.rows.rank) if self.rows is not None
+                             else shard_lengths(n, group))
+            self.kmeans = KMeansScore(labels, linear, group, lengths, rank, cfg.el2n_operands,
+                                      cfg.kmeans_k, cfg.kmeans_iters)
         # the one [n, D] fp32 buffer of the checkpoint's feature rows (n D 4 bytes: 102 MB at
         # 50 000 x 512, 10.5 GB for 1.28 M x 2048 rows on one rank), or None: logits only
         self.features = None
-        by_features = self.proto or self.nn or self.knn
+        by_features = self.proto or self.nn or self.knn or self.kmeans
         if kcenter_ckpt is not None:
             _check_width("kcenter", linear.in_features)
         if by_features or kcenter_ckpt is not None:
@@ -344,6 +462,8 @@ class ForwardScores:
         ordered after it."""
         if self.proto is not None:
             self.proto.end_checkpoint(self.features)
+        if self.kmeans is not None:
+            self.kmeans.end_checkpoint(self.features)
         keep = self._ckpts_done == self.kcenter_ckpt
         # one all-gather of the rows serves nn, the knn scores and the kcenter fill (which alone
         # needs it at its one checkpoint only)
@@ -360,7 +480,8 @@ class ForwardScores:
         self._ckpts_done += 1
 
     def _parts(self):
-        return [p for p in (self.logit, self.proto, self.nn, self.knn) if p is not None]
+        return [p for p in (self.logit, self.proto, self.nn, self.knn, self.kmeans)
+                if p is not None]
 
     def tensors(self) -> List[torch.Tensor]:
         """Every device buffer the pass and the second phase touch (for the streams'

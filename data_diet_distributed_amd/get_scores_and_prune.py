@@ -43,15 +43,18 @@ from .subset_index import json_radius, write_subset_index
 from .synthetic import state_digest
 
 
-FEATURE_SCORES = ("nn", "knn", "knn_disagree")  # from the rows the classifier consumes
+FEATURE_SCORES = ("nn", "knn", "knn_disagree", "kmeans")  # from the rows the classifier consumes
 
 
-def _feature_scores(feats, labels, num_classes, score, knn_k):
+def _feature_scores(feats, labels, num_classes, score, knn_k, kmeans_k=0, kmeans_iters=20):
     """The chosen score of FEATURE_SCORES among the visited rows `feats` [n, D] (LabelError for
     a label outside [0, C))."""
-    from .forward_scores import nearest_k, nearest_same_class
+    from .forward_scores import kmeans, nearest_k, nearest_same_class
     if score == "nn":
         return nearest_same_class(feats, labels, num_classes)
+    if score == "kmeans":
+        _capi.class_counts(labels.contiguous(), num_classes, check=True)
+        return kmeans(feats, int(kmeans_k) or num_classes, kmeans_iters)[2]
     mean, share = nearest_k(feats, labels, num_classes, knn_k)
     return mean if score == "knn" else share
 
@@ -67,12 +70,13 @@ def _score_rows(logits, labels, out, bad, score="el2n"):
 
 
 def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect=None,
-                            score="el2n", knn_k=5, keep_rows=False):
+                            score="el2n", knn_k=5, keep_rows=False, kmeans_k=0, kmeans_iters=20):
     """Scores of every example the loader yields, in visit order, plus the visited indices
     (`score`: "el2n" or one of _capi.LOGIT_STATS, from the same logits; or "nn", the distance to
     the nearest visited example of the same class, or "knn" / "knn_disagree", the mean distance
-    to the knn_k nearest visited examples and the share of them with another label, from the rows
-    `net.linear` consumes).
+    to the knn_k nearest visited examples and the share of them with another label, or "kmeans",
+    the distance to the nearest of kmeans_k centroids of the visited examples after kmeans_iters
+    Lloyd updates, from the rows `net.linear` consumes).
     A dict given as `collect` receives "labels" (the targets in visit order, int64 on the
     device) and "num_classes" (the width of the logits), for the class selection policies, and
     with keep_rows "rows": the rows `net.linear` consumes, in visit order (the kcenter fill).
@@ -113,7 +117,7 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
             hook.remove()
     if by_rows and visit:
         scores = [_feature_scores(torch.cat(feats).contiguous(), torch.cat(targets), C, score,
-                                  knn_k)]
+                                  knn_k, kmeans_k, kmeans_iters)]
     if collect is not None and keep_rows:
         collect["rows"] = torch.cat(feats).contiguous() if feats else None
     if collect is not None:
@@ -317,7 +321,7 @@ def fast_path(train_loader, net, device):
 
 
 def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, score="el2n",
-                     knn_k=5, collect=None):
+                     knn_k=5, collect=None, kmeans_k=0, kmeans_iters=20):
     """Scores in visit order + visited indices, like el2n_scores_from_loader, on the hand
     kernels: every visit batch of the loader's BatchSampler (all of size B but a ragged last
     one) is one BN group; chunks of whole batches are gathered + normalised on device.  A dict
@@ -371,7 +375,7 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
             _score_rows(logits.contiguous(), lab_d[idx], scores[c0:c1], bad, score)
         if by_rows:  # neighbours among the visited examples (LabelError inside)
             return _feature_scores(feats, lab_d[visit_d], model.linear.out_features, score,
-                                   knn_k), visit_d
+                                   knn_k, kmeans_k, kmeans_iters), visit_d
     # a label outside [0, C): the reference's one_hot raises (:17), so does this path
     _capi.check_labels(bad, model.linear.out_features, "sparse_loader")
     return scores, visit_d
@@ -422,7 +426,7 @@ def refine_fast_keep_set(train_loader, src, model, device, scores, visit, sample
 def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size, num_workers,
                   *, dataset=None, subset_index_path=None, return_indices=False,
                   fast: bool = True, refine="auto", policy="global", skip=0, score="el2n",
-                  knn_k=5, fill="score", seed_frac=0.0):
+                  knn_k=5, fill="score", seed_frac=0.0, kmeans_k=0, kmeans_iters=20):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
@@ -444,6 +448,10 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     "knn" ranks by the mean distance to the knn_k nearest visited examples of any class and
     "knn_disagree" by the share of those neighbours that carry another label (dd_knn on the same
     rows; knn_k in 1.._capi.KNN_MAX_K, fewer visited examples than knn_k + 1 raise).
+    "kmeans" ranks by the distance to the nearest of kmeans_k centroids (0: the class count; at most
+    _capi.KMEANS_MAX_K) of a k-means clustering of the visited examples' rows, kmeans_iters Lloyd
+    updates from evenly spaced visited rows (dd_kmeans_assign; fewer visited examples than
+    clusters raise).
     fill / seed_frac: how the quotas are filled (ScoreConfig.select_fill / kcenter_seed_frac):
     "score" is the rank cut; "kcenter" seeds every group with its top
     max(1, floor(seed_frac * quota)) examples by `score` and picks the rest by farthest-first
@@ -466,6 +474,11 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
             isinstance(knn_k, bool) or not isinstance(knn_k, (int, np.integer))
             or not 1 <= knn_k <= _capi.KNN_MAX_K):
         raise ValueError(f"knn_k must be an integer in 1..{_capi.KNN_MAX_K} (got {knn_k!r})")
+    if score == "kmeans":
+        for name, v, lo, hi in (("kmeans_k", kmeans_k, 0, _capi.KMEANS_MAX_K),
+                                ("kmeans_iters", kmeans_iters, 1, 1000)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+                raise ValueError(f"{name} must be an integer in {lo}..{hi} (got {v!r})")
     if refine is True and score != "el2n":
         raise ValueError("refine=True re-scores EL2N only: it needs score='el2n'")
     skip = check_selection(policy, skip, "policy", "skip", fill=fill, seed_frac=seed_frac,
@@ -486,12 +499,14 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     seen = {} if kcenter else None  # the kcenter fill needs the visited rows
     if fp is not None:
         scores, visit = el2n_scores_fast(train_loader, fp[0], fp[1], device, score=score,
-                                         knn_k=knn_k, collect=seen)
+                                         knn_k=knn_k, collect=seen, kmeans_k=kmeans_k,
+                                         kmeans_iters=kmeans_iters)
     else:
         if policy != "global":  # a class policy needs the visited targets
             seen = {}
         scores, visit = el2n_scores_from_loader(train_loader, net, device, collect=seen,
-                                                score=score, knn_k=knn_k, keep_rows=kcenter)
+                                                score=score, knn_k=knn_k, keep_rows=kcenter,
+                                                kmeans_k=kmeans_k, kmeans_iters=kmeans_iters)
     samples = _capi.keep_count(train_samples, sparsity)
     if samples < 0 or samples > scores.numel():
         raise ValueError(f"keep count {samples} outside [0, {scores.numel()}]")
@@ -532,6 +547,9 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                             "order": "loader visit order (reference semantics)",
                             "checkpoint_digests": [digest],
                             **({"knn_k": int(knn_k)} if score in ("knn", "knn_disagree") else {}),
+                            # (the resolved cluster count, as score.py records it)
+                            **({"kmeans_k": int(kmeans_k) or int(module.linear.out_features),
+                                "kmeans_iters": int(kmeans_iters)} if score == "kmeans" else {}),
                             **({} if default_rule else {
                                 "select_policy": policy, "select_skip": int(skip),
                                 "class_quota": sparse_loader.last_selection["class_quota"],

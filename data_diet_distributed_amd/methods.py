@@ -35,16 +35,25 @@ FORWARD_SCORES = FORWARD_FAMILY + NEIGHBOR_METHODS
 # Larger = more isolated / more suspicious.  They come from the EL2N forward too; FORWARD_SCORES
 # keeps its value and every decision goes through known() / pass_of().
 KNN_METHODS = ("knn", "knn_disagree")
+# The score of a row against the centroids of a k-means clustering of the WHOLE dataset's feature
+# rows (ScoreConfig.kmeans_k clusters, kmeans_iters Lloyd updates from evenly spaced seed rows):
+#   kmeans_i = || f_i - mu_{a(i)} ||_2, a(i) the nearest centroid
+# (Sorscher et al.'s self-supervised prototype distance: proto without labels; larger = more
+# atypical).  The cluster sums are exact fixed point like proto's, so the scores are bitwise
+# independent of chunks, lanes and ranks (include/dd_capi.h dd_kmeans_assign).
+CLUSTER_METHODS = ("kmeans",)
 
 
 def known(method: str) -> bool:
-    return method == "grand" or method in FORWARD_SCORES or method in KNN_METHODS
+    return (method == "grand" or method in FORWARD_SCORES or method in KNN_METHODS
+            or method in CLUSTER_METHODS)
 
 
 def pass_of(method: str) -> str:
     """The pass that computes `method`: "el2n" (the shared forward of the logit family, the
-    feature scores and the neighbour scores) or "grand"."""
-    return "el2n" if method in FORWARD_SCORES or method in KNN_METHODS else "grand"
+    feature scores, the neighbour scores and the cluster score) or "grand"."""
+    return ("el2n" if method in FORWARD_SCORES or method in KNN_METHODS
+            or method in CLUSTER_METHODS else "grand")
 
 
 def refinable(method: str) -> bool:

@@ -818,6 +818,86 @@ int dd_kcenter_greedy(const float* rows, const int64_t* ids, int64_t n, int32_t 
                       float* radius2, float* mind2, int32_t* bad, void* workspace,
                       size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------- *
+ * Distance to the nearest k-means centroid in feature space: the self-supervised prototype
+ * distance of Sorscher et al. ("Beyond neural scaling laws"), which needs no labels.  Purely
+ * additive: dd_abi_version() stays 10.
+ *
+ * Per checkpoint: the feature rows f_i (fp32 [N][D], the whole dataset), Kc clusters, `iters`
+ * Lloyd updates.  The caller drives the loop; these entry points are its steps.
+ *
+ *   seeds       mu_j = f_{s_j},  s_j = floor((2 j + 1) N / (2 Kc)),  j = 0 .. Kc - 1: rows of the
+ *               dataset in dataset order, deterministic and independent of the world size
+ *               (N >= Kc).
+ *   assignment  a(i) = argmin_j (key(i, j), j), compared lexicographically: a tie goes to the
+ *               smaller cluster id.  key(i, j) = ||mu_j||^2 - 2 f_i . mu_j is dd_nn_same_class's
+ *               key: the dot product on split MFMA (hi.hi + hi.lo + lo.hi of the `operands` halves,
+ *               fp32 accumulation, 32x32x16, D zero-padded to a multiple of 16, K order fixed by
+ *               D), ||mu_j||^2 in fp32 in an order fixed by D.  A centroid whose key is NaN (a
+ *               non-finite element) is never picked.
+ *   update      S_j = sum over {i : a(i) = j} of q(f_i) in int64, q(v) = round-to-nearest-even(v *
+ *               2^24) as in dd_class_feature_sums, n_j = |{i : a(i) = j}|;
+ *               mu_j[d] = (float)(((double)S_j[d] / (double)n_j) * 2^-24) where n_j > 0; an empty
+ *               cluster keeps its previous centroid.
+ *   score       after `iters` updates, one more assignment:
+ *               kmeans_i = sqrt(sum_d (f_i[d] - mu_{a(i)}[d])^2), in fp32 from the fp32 rows, one
+ *               row per wave in an order fixed by D (dd_proto_scores' reduction).  The MFMA
+ *               rounding decides only WHICH of two near-equidistant centroids is taken, never the
+ *               value; a row that equals its centroid scores exactly 0, and
+ *               d^2(pick) - d^2(best) <= 2 eps (||f_i||^2 + max_j ||mu_j||^2), eps as for
+ *               dd_nn_same_class.
+ *   A row with an element that is NaN, infinite or has |v| >= 2^15 (dd_class_feature_sums' rule):
+ *   assign = -1, distance NaN, nothing added to any sum or count, one added to bad[0].  A row for
+ *   which no centroid is admissible (every key NaN): assign = -1, distance NaN.
+ *
+ * dd_kmeans_assign: rows fp32 [n][D] (all of the dataset or a part), centroids fp32 [Kc][D].
+ *   sums int64 [Kc][D] and counts int64 [Kc] (both or neither) ACCUMULATE S and n over the call's
+ *   rows, and bad int64 [1] the unrepresentable rows: the caller clears them, and two calls over a
+ *   split of the rows equal one call over all of them.  assign int32 [n], dist fp32 [n] (written)
+ *   and accum fp32 [n] (accum[i] += the distance) are as above.  sums / counts, assign, dist and
+ *   accum may each be NULL, not all of them.  repack_rows != 0 splits the rows into operand halves
+ *   (and writes the centroids' ids) in the workspace; with 0 what an earlier call with the same
+ *   rows, n, Kc, D and operands left there is used (the rows do not change between the iterations
+ *   of a run).  The
+ *   centroids are split on every call.  A 256-thread workgroup owns 128 rows: it searches the
+ *   centroids 128 at a time, takes the values one row per wave, ranks its 128 (pick, position)
+ *   pairs in LDS and walks its rows in cluster order, summing in int64 registers while the cluster
+ *   stays the same: about (n / 128) min(128, clusters met in the tile) D 64-bit atomics, not n D,
+ *   and no global sort.  No kernel waits for another workgroup.
+ *
+ * dd_kmeans_centroids: the update above, in place on centroids fp32 [Kc][D]; where counts[j] <= 0
+ *   the centroid is left untouched.
+ *
+ * Invariance: a key depends on the row, the centroid and D alone, and the minimum of (key, j)
+ * under one total order does not depend on the order in which the centroids are met, so a(i) is a
+ * function of row i and the centroids; the sums are exact integers, so S and n are functions of
+ * the row SET and the centroids; the centroid formula is a function of S and n alone.  By
+ * induction over the iterations every centroid, assignment and distance is bitwise independent of
+ * the chunk size, the lanes, the launch geometry, the row order, the split of the rows over calls
+ * and the world size (the ranks add their S and n with an exact integer all-reduce).
+ *
+ * Limits: 1 <= Kc <= DD_KMEANS_MAX_K, 1 <= D <= 4096, 0 <= n < 2^31, operands DD_OPERANDS_F16X3
+ * or DD_OPERANDS_BF16X3; N < 2^24 over the whole dataset (a cluster may take every row, and
+ * |q| < 2^39), which the caller ensures.  Outside them, a NULL buffer the call would touch, no
+ * output requested, or a workspace that is too small or not 16-byte aligned is DD_EINVAL with a
+ * message before any launch.  n == 0 returns DD_OK.  The workspace (dd_kmeans_workspace_bytes:
+ * host only, 0 for bad arguments) holds the halves of the rows and of the centroids,
+ * 4 (n + Kc) pad16(D) bytes, 4 Kc bytes of norms and 8 Kc bytes of ids, each region rounded up to
+ * 256.  No allocation, no synchronisation inside (graph-capturable); plain vector stores and
+ * 64-bit integer atomics only, no float atomics.
+ * ---------------------------------------------------------------------------------------- */
+#define DD_KMEANS_MAX_K 4096
+
+size_t dd_kmeans_workspace_bytes(int64_t n, int32_t Kc, int32_t D, int32_t operands);
+
+int dd_kmeans_assign(const float* rows, int64_t n, const float* centroids, int32_t Kc, int32_t D,
+                     int32_t operands, int32_t repack_rows, int64_t* sums, int64_t* counts,
+                     int64_t* bad, int32_t* assign, float* dist, float* accum, void* workspace,
+                     size_t workspace_bytes, void* stream);
+
+int dd_kmeans_centroids(const int64_t* sums, const int64_t* counts, int32_t Kc, int32_t D,
+                        float* centroids, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
