@@ -24,7 +24,7 @@ all: $(LIB)
 # so no result depends on it and it can go when the advisory does.  The host pass of hipcc notes
 # "not a recognized feature" for it: harmless, -Xarch_device takes no option with an argument.
 # The older units keep the flags their recorded results and timings were taken with.
-$(OBJDIR)/dd_kmeans.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+$(OBJDIR)/dd_kmeans.o $(OBJDIR)/dd_kmedoids.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(OBJDIR)/%.o: data_diet_distributed_amd/csrc/%.hip $(HDR)
 	@mkdir -p $(OBJDIR)

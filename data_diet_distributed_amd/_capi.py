@@ -50,6 +50,7 @@ EXPORTS = (
     "dd_nn_workspace_bytes", "dd_nn_same_class",
     "dd_knn_workspace_bytes", "dd_knn",
     "dd_kcenter_workspace_bytes", "dd_kcenter_seed_batch", "dd_kcenter_greedy",
+    "dd_kmedoids_workspace_bytes", "dd_kmedoids_greedy",
     "dd_kmeans_workspace_bytes", "dd_kmeans_assign", "dd_kmeans_centroids",
 )
 
@@ -112,6 +113,9 @@ def lib():
                 "dd_kcenter_seed_batch": (I32, [I32, I32]),
                 "dd_kcenter_greedy": (I32, [P, P, I64, I32, P, I32, P, P, I64, P, I64, I32, I32,
                                             P, P, P, P, P, SZ, P]),
+                "dd_kmedoids_workspace_bytes": (SZ, [I64, I32, I32, P, I64, I32]),
+                "dd_kmedoids_greedy": (I32, [P, P, I64, I32, P, P, I32, P, P, I64, P, I64, I32,
+                                             I32, I32, P, P, P, P, P, SZ, P]),
                 "dd_kmeans_workspace_bytes": (SZ, [I64, I32, I32, I32]),
                 "dd_kmeans_assign": (I32, [P, I64, P, I32, I32, I32, I32, P, P, P, P, P, P, P,
                                            SZ, P]),
@@ -649,6 +653,75 @@ def kcenter_workspace_bytes(n: int, D: int, G: int, steps: int) -> int:
     return int(lib().dd_kcenter_workspace_bytes(int(n), int(D), int(G), int(steps)))
 
 
+def _greedy_check(what, rows, sizes, seeds, seed_counts, picks, groups, seed_batch, blocks):
+    """The host rejections kcenter_greedy and kmedoids_greedy share, under the caller's name.
+    Returns (n, D, G, sizes, seed_counts, picks, seed_batch, blocks) as host ints."""
+    _dev(rows, torch.float32, "rows", 2)
+    n, D = rows.shape
+    sizes, seed_counts, picks = ([int(v) for v in x] for x in (sizes, seed_counts, picks))
+    G = len(sizes)
+    if not 1 <= G <= KCENTER_MAX_GROUPS:
+        raise ValueError(f"{what}: need 1 <= G <= {KCENTER_MAX_GROUPS} (got {G})")
+    if len(seed_counts) != G or len(picks) != G:
+        raise ValueError(f"{what}: sizes, seed_counts and picks need one entry per group")
+    if any(v < 0 for v in sizes + seed_counts + picks) or sum(sizes) > n:
+        raise ValueError(f"{what}: negative count, or more group members than rows")
+    for g in range(G):
+        if seed_counts[g] + picks[g] > sizes[g]:
+            raise ValueError(f"{what}: group {g} of {sizes[g]} rows cannot keep "
+                             f"{seed_counts[g]} seeds + {picks[g]} picks")
+        if picks[g] and not seed_counts[g]:
+            raise ValueError(f"{what}: group {g} has picks but no seed")
+    _dev(seeds, torch.int64, "seeds", 1)
+    if seeds.numel() != sum(seed_counts):
+        raise ValueError(f"{what}: {seeds.numel()} seeds, seed_counts sum to "
+                         f"{sum(seed_counts)}")
+    if groups is None and G != 1:
+        raise ValueError(f"{what}: G > 1 needs `groups`")
+    seed_batch, blocks = int(seed_batch), int(blocks)
+    if not 0 <= seed_batch <= KCENTER_MAX_SEED_BATCH:
+        raise ValueError(f"{what}: seed_batch must be in 0..{KCENTER_MAX_SEED_BATCH}")
+    if not 0 <= blocks <= KCENTER_MAX_BLOCKS:
+        raise ValueError(f"{what}: blocks must be in 0..{KCENTER_MAX_BLOCKS}")
+    return n, D, G, sizes, seed_counts, picks, seed_batch, blocks
+
+
+def _greedy_sort(rows, ids, groups, G, sizes, seeds, seed_counts, picks, stat):
+    """The rows of a greedy fill in group order, ascending id inside a group (two stable sorts;
+    none where the rows already are: one group, ids ascending by construction); stat[1] takes
+    the ids outside [0, 2^31).  Returns (rows, ids, order or None, the seeds as sorted positions,
+    off, seed_off, picks), all on the device."""
+    n, dev = rows.shape[0], rows.device
+    order = None
+    if ids is not None:
+        _dev(ids, torch.int64, "ids", 1)
+        if ids.numel() != n:
+            raise ValueError("ids must have one entry per row")
+        stat[1:2] = ((ids < 0) | (ids >= KCENTER_ID_LIMIT)).sum().to(torch.int32)
+        order = torch.argsort(ids, stable=True)
+    else:
+        ids = torch.arange(n, dtype=torch.int64, device=dev)
+    if groups is not None:
+        _dev(groups, torch.int64, "groups", 1)
+        if groups.numel() != n:
+            raise ValueError("groups must have one entry per row")
+        key = torch.where((groups >= 0) & (groups < G), groups, torch.full_like(groups, G))
+        if order is None:
+            order = torch.argsort(key, stable=True)
+        else:
+            order = order[torch.argsort(key[order], stable=True)]
+    pos = seeds
+    if order is not None:
+        rows, ids = rows.index_select(0, order), ids.index_select(0, order)
+        inv = torch.empty_like(order)
+        inv[order] = torch.arange(n, dtype=torch.int64, device=dev)
+        pos = inv[seeds]
+    pos = torch.sort(pos)[0].contiguous()  # group order: a group's seeds are contiguous
+    off, seed_off = (torch.tensor([0] + list(itertools.accumulate(v)),
+                                  dtype=torch.int64).to(dev) for v in (sizes, seed_counts))
+    return rows, ids, order, pos, off, seed_off, torch.tensor(picks, dtype=torch.int64).to(dev)
+
+
 def kcenter_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor, seed_counts,
                    picks, *, seed_batch: int = 0, blocks: int = 0, check: bool = True):
     """Farthest-first traversal inside groups (dd_kcenter_greedy).  rows fp32 [n, D] in ANY order;
@@ -668,34 +741,9 @@ def kcenter_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor, 
     With check the two counts are read back (one sync) and either raises ValueError; check=False
     leaves them to the caller.  seed_batch / blocks: centres per seed launch and workgroups per
     group (0: chosen by the library); no output depends on either."""
-    _dev(rows, torch.float32, "rows", 2)
-    n, D = rows.shape
+    n, D, G, sizes, seed_counts, picks, seed_batch, blocks = _greedy_check(
+        "kcenter_greedy", rows, sizes, seeds, seed_counts, picks, groups, seed_batch, blocks)
     dev = rows.device
-    sizes, seed_counts, picks = ([int(v) for v in x] for x in (sizes, seed_counts, picks))
-    G = len(sizes)
-    if not 1 <= G <= KCENTER_MAX_GROUPS:
-        raise ValueError(f"kcenter_greedy: need 1 <= G <= {KCENTER_MAX_GROUPS} (got {G})")
-    if len(seed_counts) != G or len(picks) != G:
-        raise ValueError("kcenter_greedy: sizes, seed_counts and picks need one entry per group")
-    if any(v < 0 for v in sizes + seed_counts + picks) or sum(sizes) > n:
-        raise ValueError("kcenter_greedy: negative count, or more group members than rows")
-    for g in range(G):
-        if seed_counts[g] + picks[g] > sizes[g]:
-            raise ValueError(f"kcenter_greedy: group {g} of {sizes[g]} rows cannot keep "
-                             f"{seed_counts[g]} seeds + {picks[g]} picks")
-        if picks[g] and not seed_counts[g]:
-            raise ValueError(f"kcenter_greedy: group {g} has picks but no seed")
-    _dev(seeds, torch.int64, "seeds", 1)
-    if seeds.numel() != sum(seed_counts):
-        raise ValueError(f"kcenter_greedy: {seeds.numel()} seeds, seed_counts sum to "
-                         f"{sum(seed_counts)}")
-    if groups is None and G != 1:
-        raise ValueError("kcenter_greedy: G > 1 needs `groups`")
-    seed_batch, blocks = int(seed_batch), int(blocks)
-    if not 0 <= seed_batch <= KCENTER_MAX_SEED_BATCH:
-        raise ValueError(f"kcenter_greedy: seed_batch must be in 0..{KCENTER_MAX_SEED_BATCH}")
-    if not 0 <= blocks <= KCENTER_MAX_BLOCKS:
-        raise ValueError(f"kcenter_greedy: blocks must be in 0..{KCENTER_MAX_BLOCKS}")
     steps = max(picks)
     need = int(lib().dd_kcenter_workspace_bytes(n, D, G, steps))
     if need == 0:
@@ -705,36 +753,8 @@ def kcenter_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor, 
     radius2 = torch.full((steps, G), -1.0, dtype=torch.float32, device=dev)
     mind2 = torch.full((n,), float("inf"), dtype=torch.float32, device=dev)
     if n:
-        # group order, ascending id inside a group (two stable sorts; none where the rows
-        # already are: one group, ids ascending by construction)
-        order = None
-        if ids is not None:
-            _dev(ids, torch.int64, "ids", 1)
-            if ids.numel() != n:
-                raise ValueError("ids must have one entry per row")
-            stat[1:2] = ((ids < 0) | (ids >= KCENTER_ID_LIMIT)).sum().to(torch.int32)
-            order = torch.argsort(ids, stable=True)
-        else:
-            ids = torch.arange(n, dtype=torch.int64, device=dev)
-        if groups is not None:
-            _dev(groups, torch.int64, "groups", 1)
-            if groups.numel() != n:
-                raise ValueError("groups must have one entry per row")
-            key = torch.where((groups >= 0) & (groups < G), groups, torch.full_like(groups, G))
-            if order is None:
-                order = torch.argsort(key, stable=True)
-            else:
-                order = order[torch.argsort(key[order], stable=True)]
-        pos = seeds
-        if order is not None:
-            rows, ids = rows.index_select(0, order), ids.index_select(0, order)
-            inv = torch.empty_like(order)
-            inv[order] = torch.arange(n, dtype=torch.int64, device=dev)
-            pos = inv[seeds]
-        pos = torch.sort(pos)[0].contiguous()  # group order: a group's seeds are contiguous
-        off, seed_off = (torch.tensor([0] + list(itertools.accumulate(v)),
-                                      dtype=torch.int64).to(dev) for v in (sizes, seed_counts))
-        picks_d = torch.tensor(picks, dtype=torch.int64).to(dev)
+        rows, ids, order, pos, off, seed_off, picks_d = _greedy_sort(
+            rows, ids, groups, G, sizes, seeds, seed_counts, picks, stat)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         mind2_s = mind2 if order is None else torch.empty_like(mind2)
         e0 = _t0(rows, always=True)
@@ -757,6 +777,77 @@ def kcenter_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor, 
     if check:
         check_kcenter(stat.tolist())
     return picked, radius2, mind2, stat
+
+
+KMEDOIDS_MAX_GROUP_ROWS = 16384  # DD_KMEDOIDS_MAX_GROUP_ROWS
+
+
+def kmedoids_workspace_bytes(n: int, D: int, sizes, steps: int, operands: str = "f16x3") -> int:
+    """Bytes of kmedoids_greedy's workspace (dd_kmedoids_workspace_bytes; 0 for sizes outside
+    the entry point's limits: a group above KMEDOIDS_MAX_GROUP_ROWS among them)."""
+    sizes = [int(v) for v in sizes]
+    return int(lib().dd_kmedoids_workspace_bytes(int(n), int(D), len(sizes),
+                                                 (ctypes.c_int64 * len(sizes))(*sizes),
+                                                 int(steps), OPERANDS.get(operands, -1)))
+
+
+def kmedoids_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor, seed_counts,
+                    picks, *, operands: str = "f16x3", seed_batch: int = 0, blocks: int = 0,
+                    check: bool = True):
+    """The greedy k-medoids fill inside groups (dd_kmedoids_greedy): every pick is the row whose
+    addition lowers the group's sum of squared distances to the nearest kept row the most, a tie
+    to the smaller id.  The arguments, the sorting, the host rejections and `stat` are
+    kcenter_greedy's; `operands` names the split-MFMA halves of the distance matrix ("f16x3" or
+    "bf16x3").  A group holds at most KMEDOIDS_MAX_GROUP_ROWS rows (its n_g x n_g fp32 distance
+    matrix lives in the workspace for the whole call).
+
+    Returns (picked int64 [steps, G], gain fp32 [steps, G], cur fp32 [n], stat int32 [2]):
+    picked[t, g] is the id group g takes at step t and gain[t, g] the decrease of the group's sum
+    it brought (both -1 for t >= picks[g]); cur, in the order of `rows`, is every row's final
+    squared distance to its nearest kept row (-1: kept; +inf: a group that keeps nothing, or no
+    group).  No output depends on seed_batch or blocks."""
+    what = "kmedoids_greedy"
+    n, D, G, sizes, seed_counts, picks, seed_batch, blocks = _greedy_check(
+        what, rows, sizes, seeds, seed_counts, picks, groups, seed_batch, blocks)
+    if operands not in ("f16x3", "bf16x3"):
+        raise ValueError(f"{what}: operands must be 'f16x3' or 'bf16x3' (got {operands!r})")
+    if max(sizes) > KMEDOIDS_MAX_GROUP_ROWS:
+        raise ValueError(f"{what}: a group of {max(sizes)} rows is above the "
+                         f"{KMEDOIDS_MAX_GROUP_ROWS} whose distance matrix one call holds")
+    dev = rows.device
+    steps = max(picks)
+    sizes_h = (ctypes.c_int64 * G)(*sizes)
+    need = int(lib().dd_kmedoids_workspace_bytes(n, D, G, sizes_h, steps, OPERANDS[operands]))
+    if need == 0:
+        raise ValueError(f"{what}: unsupported size n={n}, D={D}, G={G}")
+    stat = torch.zeros(2, dtype=torch.int32, device=dev)
+    picked = torch.full((steps, G), -1, dtype=torch.int64, device=dev)
+    gain = torch.full((steps, G), -1.0, dtype=torch.float32, device=dev)
+    cur = torch.full((n,), float("inf"), dtype=torch.float32, device=dev)
+    if n:
+        rows, ids, order, pos, off, seed_off, picks_d = _greedy_sort(
+            rows, ids, groups, G, sizes, seeds, seed_counts, picks, stat)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        cur_s = cur if order is None else torch.empty_like(cur)
+        e0 = _t0(rows, always=True)
+        rc = lib().dd_kmedoids_greedy(
+            _dev(rows, torch.float32, "rows"), _dev(ids, torch.int64, "ids"), n, D,
+            _dev(off, torch.int64, "off"), sizes_h, G,
+            _opt(pos if pos.numel() else None, torch.int64, "seeds"),
+            _dev(seed_off, torch.int64, "seed_off"), max(seed_counts),
+            _dev(picks_d, torch.int64, "picks"), steps, OPERANDS[operands], seed_batch, blocks,
+            _opt(picked if steps else None, torch.int64, "picked"),
+            _opt(gain if steps else None, torch.float32, "gain"),
+            _dev(cur_s, torch.float32, "cur"), ctypes.c_void_p(stat.data_ptr()),
+            _dev(ws, torch.uint8, "workspace"), need, _stream(rows))
+        _check(rc, "dd_kmedoids_greedy")
+        # the matrices written once, then streamed by every pick launch a group takes part in
+        _t1(e0, "select", 4.0 * sum(s * s * (1 + p) for s, p in zip(sizes, picks)), rows)
+        if order is not None:
+            cur[order] = cur_s
+    if check:
+        check_kcenter(stat.tolist())
+    return picked, gain, cur, stat
 
 
 def check_kcenter(stat):

@@ -31,6 +31,7 @@ DEFAULTS = {
     "select_skip": 0,                 # ranks skipped from the top before the k kept ones
     "select_fill": "score",           # score (the rank cut) | kcenter (coverage: greedy k-center)
     "kcenter_seed_frac": 0.0,         # share of a quota seeded by the score (at least one seed)
+    "kcenter_objective": "radius",    # radius (farthest-first) | inertia (greedy k-medoids)
     "kcenter_ckpt": -1,               # the checkpoint whose feature rows span the space
     "score_checkpoints": 1,           # K (seed{k}/ckpt_{epoch}.pth when K > 1)
     "score_epoch": 19,

@@ -426,7 +426,8 @@ def refine_fast_keep_set(train_loader, src, model, device, scores, visit, sample
 def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size, num_workers,
                   *, dataset=None, subset_index_path=None, return_indices=False,
                   fast: bool = True, refine="auto", policy="global", skip=0, score="el2n",
-                  knn_k=5, fill="score", seed_frac=0.0, kmeans_k=0, kmeans_iters=20):
+                  knn_k=5, fill="score", seed_frac=0.0, kmeans_k=0, kmeans_iters=20,
+                  objective="radius"):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
@@ -458,10 +459,15 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     traversal of the visited examples' feature rows (the rows the classifier consumes, from the
     same single forward; dd_kcenter_greedy), a tie to the earlier visited example.  It needs
     skip = 0 and is never refined; `sparse_loader.last_selection` records the seeds and radii.
+    objective (ScoreConfig.kcenter_objective; checked whatever the fill): "radius" is that
+    traversal; "inertia" picks, one at a time, the example that lowers its group's sum of squared
+    distances to the nearest kept example the most (greedy k-medoids, dd_kmedoids_greedy; a
+    group of at most _capi.KMEDOIDS_MAX_GROUP_ROWS examples, so large sets need a class policy),
+    and the record also holds each group's inertia.
     "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
     over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
     score="el2n"."""
-    from .methods import check_selection
+    from .methods import check_objective, check_selection
     from .scoring import normalize_refine, select_with_policy
     refine = normalize_refine(refine)
     if score in ("variability", "grand", "proto"):
@@ -483,6 +489,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
         raise ValueError("refine=True re-scores EL2N only: it needs score='el2n'")
     skip = check_selection(policy, skip, "policy", "skip", fill=fill, seed_frac=seed_frac,
                            fill_name="fill", frac_name="seed_frac")
+    check_objective(objective, "objective")
     kcenter = fill == "kcenter"
     default_rule = policy == "global" and skip == 0 and not kcenter
     if refine is True and not default_rule:
@@ -522,7 +529,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
             labels_visit, ncls = seen["labels"], seen["num_classes"] or 1
         pos, sparse_loader.last_selection = select_with_policy(
             scores.contiguous(), labels_visit, ncls, samples, policy, int(skip), fill=fill,
-            seed_frac=seed_frac, rows=seen["rows"] if kcenter else None)
+            seed_frac=seed_frac, rows=seen["rows"] if kcenter else None, objective=objective)
         kept = visit[pos]
     elif fp is not None and refine is True and 0 < samples < scores.numel():
         pos, sparse_loader.last_refine = refine_fast_keep_set(
@@ -558,7 +565,11 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                                 "select_fill": fill, "kcenter_seed_frac": float(seed_frac),
                                 "class_seeds": sparse_loader.last_selection["class_seeds"],
                                 "radius": json_radius(
-                                    sparse_loader.last_selection["radius"])})})
+                                    sparse_loader.last_selection["radius"])}),
+                            **({} if not kcenter or objective == "radius" else {
+                                "kcenter_objective": objective,
+                                "inertia": json_radius(
+                                    sparse_loader.last_selection["inertia"])})})
     sparse_train_loader = DataLoader(train_subset, batch_size=batch_size, shuffle=True,
                                      num_workers=num_workers)
     if return_indices:

@@ -104,6 +104,23 @@ def check_fill(fill, seed_frac, skip=0, *, fill_name="select_fill",
     return float(seed_frac)
 
 
+# What the centre-based fill ("kcenter") optimises once a group is seeded:
+#   "radius"   the LARGEST distance from a dropped row to a kept one: farthest-first traversal
+#              (dd_kcenter_greedy).  Its picks are each group's outliers.
+#   "inertia"  the SUM of the squared distances of all rows to their nearest kept row: the greedy
+#              k-medoids / facility-location rule (dd_kmedoids_greedy), each pick the row that
+#              lowers the sum the most.  Its picks are representative rows of dense regions.
+KCENTER_OBJECTIVES = ("radius", "inertia")
+
+
+def check_objective(objective, name="kcenter_objective") -> str:
+    """ScoreConfig's kcenter_objective, and select_with_policy's / sparse_loader's `objective`
+    under their own name: one of KCENTER_OBJECTIVES, checked whatever the fill."""
+    if objective not in KCENTER_OBJECTIVES:
+        raise ValueError(f"{name} must be one of {KCENTER_OBJECTIVES} (got {objective!r})")
+    return objective
+
+
 def seed_counts(quotas, seed_frac: float):
     """Seeds per group of the kcenter fill: max(1, floor(seed_frac * q)) for a quota q > 0, none
     for q = 0 (never more than q: seed_frac <= 1)."""

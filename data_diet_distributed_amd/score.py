@@ -21,7 +21,9 @@ rest (config.DEFAULTS):
   select_skip        ranks skipped from the top before the kept window (--skip)
   select_fill        score (the rank cut) | kcenter: coverage, the greedy k-center fill of the
                      quotas over the pooled feature rows (--fill); kcenter_seed_frac: the share
-                     of a quota seeded by the score; kcenter_ckpt: whose rows (default: the last)
+                     of a quota seeded by the score; kcenter_ckpt: whose rows (default: the last);
+                     kcenter_objective: radius (farthest-first) | inertia (greedy k-medoids,
+                     --fill-objective)
   bn_mode            EL2N BatchNorm: batch|train (reference) or running|eval
   pegrad_method      auto | direct | ghost             grand_batch   GraNd chunk
   score_gpus         ranks (one per GPU; self-launched here, or run under torchrun)
@@ -146,6 +148,7 @@ def engine_config(cfg):
                        select_fill=str(cfg.get("select_fill", "score")),
                        kcenter_seed_frac=float(cfg.get("kcenter_seed_frac", 0.0)),
                        kcenter_ckpt=int(cfg.get("kcenter_ckpt", -1)),
+                       kcenter_objective=cfg.get("kcenter_objective", "radius"),
                        **SCORE_PRECISIONS[prec])
 
 
@@ -206,6 +209,9 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
                         kcenter_ckpt=ecfg.kcenter_ckpt % K, select_policy=sel["policy"],
                         class_quota=sel["class_quota"], class_seeds=sel["class_seeds"],
                         radius=json_radius(sel["radius"]))
+            if sel.get("objective", "radius") != "radius":  # (the default: metadata unchanged)
+                meta.update(kcenter_objective=sel["objective"],
+                            inertia=json_radius(sel["inertia"]))
         out_path = out_path or cfg.get("subset_index_path")
         if out_path:
             path = write_subset_index(out_path, kept_np, meta)
@@ -232,6 +238,9 @@ def parse(argv=None):
                     help="ranks skipped from the top (default: select_skip of the config)")
     ap.add_argument("--fill", default=None, choices=("score", "kcenter"),
                     help="how the quotas are filled (default: select_fill of the config)")
+    ap.add_argument("--fill-objective", default=None, choices=("radius", "inertia"),
+                    help="what the kcenter fill minimises (default: kcenter_objective of the "
+                         "config)")
     return ap.parse_args(argv)
 
 
@@ -244,6 +253,8 @@ def main(argv=None):
         cfg["select_skip"] = args.skip
     if args.fill is not None:
         cfg["select_fill"] = args.fill
+    if args.fill_objective is not None:
+        cfg["kcenter_objective"] = args.fill_objective
     gpus = args.gpus or int(cfg.get("score_gpus", 1))
     if gpus > 1 and not launch.under_launcher():
         rest = list(sys.argv[1:] if argv is None else argv)

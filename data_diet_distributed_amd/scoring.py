@@ -50,8 +50,8 @@ from .forward_scores import (ForwardScores, check_class_sizes,  # noqa: F401
                              check_no_singleton_class, ensemble_mean, nearest_same_class)
 from .methods import (CLUSTER_METHODS, FEATURE_METHODS, FORWARD_FAMILY,  # noqa: F401
                       FORWARD_SCORES, KNN_METHODS, LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS,
-                      SELECT_FILLS, SELECT_POLICIES, check_fill, check_selection, known,
-                      pass_of, refinable, seed_counts)
+                      SELECT_FILLS, SELECT_POLICIES, check_fill, check_objective,
+                      check_selection, known, pass_of, refinable, seed_counts)
 from .resnet import ResNet
 
 MEAN = (0.4914, 0.4822, 0.4465)  # reference data/loader.py:10
@@ -151,9 +151,16 @@ class ScoreConfig:
     # by default) picks the other q_g - m_g (select_with_policy; dd_kcenter_greedy).  It needs
     # select_skip = 0, is never refined (refine=True is rejected, "auto" behaves as False), and
     # last_selection records the seeds and each group's covering radius.
+    # kcenter_objective (methods.KCENTER_OBJECTIVES) is what the picks minimise: "radius" is the
+    # farthest-first traversal above; "inertia" takes, pick by pick, the row that lowers the
+    # group's sum of squared distances to the nearest kept row the most (greedy k-medoids,
+    # dd_kmedoids_greedy: representative rows where "radius" takes the outliers; a group holds at
+    # most _capi.KMEDOIDS_MAX_GROUP_ROWS rows), and last_selection also records each group's
+    # inertia.  It is validated whatever the fill, like kcenter_seed_frac.
     select_fill: str = "score"
     kcenter_seed_frac: float = 0.0
     kcenter_ckpt: int = -1
+    kcenter_objective: str = "radius"
 
     def __post_init__(self):
         self.methods = tuple(self.methods)
@@ -196,6 +203,7 @@ class ScoreConfig:
                                            fill=self.select_fill,
                                            seed_frac=self.kcenter_seed_frac)
         self.kcenter_seed_frac = float(self.kcenter_seed_frac)
+        check_objective(self.kcenter_objective)
         if isinstance(self.kcenter_ckpt, bool) or not isinstance(self.kcenter_ckpt,
                                                                  (int, np.integer)):
             raise ValueError(f"kcenter_ckpt must be an integer (got {self.kcenter_ckpt!r})")
@@ -261,7 +269,8 @@ def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
 
 def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: str = "global",
                        skip: int = 0, check_nan: bool = True, fill: str = "score",
-                       seed_frac: float = 0.0, rows: Optional[torch.Tensor] = None):
+                       seed_frac: float = 0.0, rows: Optional[torch.Tensor] = None,
+                       objective: str = "radius"):
     """The keep-set of `k` of the n = keys.numel() examples under a selection policy
     (ScoreConfig.select_policy / select_skip), in dd_select_topk's order: key descending, ties
     by ascending index.  `labels` (int64 [n], on the keys' device) and `num_classes` are read
@@ -282,7 +291,15 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     group's covering radius sqrt(max over its unkept rows of the squared distance to the
     nearest kept row): 0 where every row is kept, +inf for a group that keeps none of its
     rows (the artefact's .json records that as null).  The NaN count of the keys, the
-    non-finite rows and the ids are read once, after the loop; any raises ValueError."""
+    non-finite rows and the ids are read once, after the loop; any raises ValueError.
+
+    objective="inertia" (ScoreConfig.kcenter_objective; read by the kcenter fill, checked
+    always): dd_kmedoids_greedy makes the picks instead, each the row that lowers its group's
+    sum of squared distances to the nearest kept row the most.  The seeds, the order of `kept`
+    and "radius" are as above, and the record also gets "objective" and "inertia": per group that
+    sum over its unkept rows at the end (+inf for a non-empty group that keeps nothing), from
+    the same one read.  A group holds at most _capi.KMEDOIDS_MAX_GROUP_ROWS rows, so "global"
+    serves small sets only: a larger one raises and names the class policies."""
     if policy not in SELECT_POLICIES:
         raise ValueError(f"select policy must be one of {SELECT_POLICIES} (got {policy!r})")
     n, k, skip = keys.numel(), int(k), int(skip)
@@ -291,17 +308,25 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     # (a public entry: tools and tests call it without a ScoreConfig in front)
     seed_frac = check_fill(fill, seed_frac, skip, fill_name="fill", frac_name="seed_frac",
                            skip_name="skip")
+    check_objective(objective, "objective")
     rec = {"policy": policy, "skip": skip, "class_counts": None, "class_skip": None,
            "class_quota": None}
     if fill == "kcenter":
         rec.update(fill=fill, class_seeds=None, radius=None)
+        if objective != "radius":
+            rec.update(objective=objective, inertia=None)
         if rows is None or rows.dim() != 2 or rows.shape[0] != n:
             raise ValueError(f"fill='kcenter' needs rows [n = {n}, D] (got "
                              f"{None if rows is None else tuple(rows.shape)})")
     if policy == "global":
         if fill == "kcenter":
+            if objective == "inertia" and n > _capi.KMEDOIDS_MAX_GROUP_ROWS:
+                raise ValueError(f"objective='inertia' under policy='global' holds one n x n "
+                                 f"distance matrix: n = {n} is above "
+                                 f"{_capi.KMEDOIDS_MAX_GROUP_ROWS}; use a class policy "
+                                 f"('stratified' or 'balanced'), whose groups are the classes")
             return _kcenter_fill(keys, None, [n], [k], rows.contiguous(), seed_frac, rec,
-                                 check_nan)
+                                 check_nan, objective)
         kept = _capi.select_topk(keys, skip + k, check_nan=check_nan)[0]
         return (kept[skip:] if skip else kept), rec
     C = int(num_classes)
@@ -315,14 +340,16 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     q = apportion(k, [a - b for a, b in zip(n_c, s)], policy)
     rec.update(class_counts=n_c, class_skip=s, class_quota=q)
     if fill == "kcenter":
-        return _kcenter_fill(keys, labels, n_c, q, rows.contiguous(), seed_frac, rec, check_nan)
+        return _kcenter_fill(keys, labels, n_c, q, rows.contiguous(), seed_frac, rec, check_nan,
+                             objective)
     kept = _capi.select_topk_by_class(keys, labels, C, s, q, k_total=k, check=check_nan)[0]
     return kept, rec
 
 
-def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan):
+def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan,
+                  objective="radius"):
     """select_with_policy's kcenter fill over the groups `labels` (None: one group) of `sizes`
-    members with `quotas`; completes and returns (kept, rec)."""
+    members with `quotas`, the picks by `objective`; completes and returns (kept, rec)."""
     G, dev = len(sizes), keys.device
     m = seed_counts(quotas, seed_frac)
     if labels is None:
@@ -331,8 +358,8 @@ def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan):
         seeds, nan, _ = _capi.select_topk_by_class(keys, labels, G, [0] * G, m, k_total=sum(m),
                                                    check=False)
     picks = [q - a for q, a in zip(quotas, m)]
-    picked, _, mind2, stat = _capi.kcenter_greedy(rows, None, labels, sizes, seeds, m, picks,
-                                                  check=False)
+    greedy = _capi.kmedoids_greedy if objective == "inertia" else _capi.kcenter_greedy
+    picked, _, mind2, stat = greedy(rows, None, labels, sizes, seeds, m, picks, check=False)
     # by (step, group): the (t, g) with t < picks[g], their positions built on the host (a
     # boolean mask would make the host wait for the size of its result)
     p = np.asarray(picks, dtype=np.int64)
@@ -343,13 +370,20 @@ def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan):
     grp = labels if labels is not None else torch.zeros(keys.numel(), dtype=torch.int64,
                                                         device=dev)
     far.scatter_reduce_(0, grp, mind2.clamp(min=0), reduce="amax", include_self=True)
+    extra = []
+    if objective == "inertia":  # the sum left per group (kept rows add 0), in float64
+        extra = [torch.zeros(G, dtype=torch.float64, device=dev).scatter_add_(
+            0, grp, mind2.clamp(min=0).to(torch.float64))]
     # the one read after the loop: the keys' NaN count, the rows' and ids' counts, the radii
+    # (and the inertias)
     host = torch.cat([nan.to(torch.float64), stat.to(torch.float64),
-                      far.to(torch.float64)]).tolist()
+                      far.to(torch.float64)] + extra).tolist()
     if check_nan and host[0]:
         raise ValueError(f"{int(host[0])} NaN score(s): the keep-set is undefined")
     _capi.check_kcenter(host[1:3])
-    rec.update(class_seeds=m, radius=[float(np.sqrt(v)) for v in host[3:]])
+    rec.update(class_seeds=m, radius=[float(np.sqrt(v)) for v in host[3:3 + G]])
+    if objective == "inertia":
+        rec.update(inertia=[float(v) for v in host[3 + G:]])
     return kept, rec
 
 
@@ -1006,6 +1040,7 @@ class ScoringEngine:
             kept, self.last_selection = select_with_policy(
                 keys, all_labels, self.models[0].linear.out_features, k, c.select_policy,
                 c.select_skip, check_nan, fill=c.select_fill, seed_frac=c.kcenter_seed_frac,
+                objective=c.kcenter_objective,
                 rows=self._kcenter_rows if c.select_fill == "kcenter" else None)
             return kept
 

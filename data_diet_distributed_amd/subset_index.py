@@ -37,8 +37,8 @@ def write_subset_index(path: str, indices, meta: dict | None = None) -> str:
 
 
 def json_radius(radius):
-    """A kcenter selection's radii for the metadata: +inf (a group that keeps none of its rows)
-    becomes None, which JSON writes as null (`Infinity` is no JSON token)."""
+    """A kcenter selection's radii (or inertias) for the metadata: +inf (a group that keeps none
+    of its rows) becomes None, which JSON writes as null (`Infinity` is no JSON token)."""
     return [float(r) if np.isfinite(r) else None for r in radius]
 
 

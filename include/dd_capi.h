@@ -819,6 +819,78 @@ int dd_kcenter_greedy(const float* rows, const int64_t* ids, int64_t n, int32_t 
                       size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------- *
+ * Greedy k-medoids (the sum criterion of coverage: facility location, CRAIG's selection rule)
+ * over feature rows, inside groups: the keep-set whose picks lower the total squared distance of
+ * all rows to their nearest kept row the most.  Purely additive: dd_abi_version() stays 10.
+ *
+ * rows, ids, off, seeds, seed_off, max_seeds, picks and steps are dd_kcenter_greedy's (rows in
+ * GROUP ORDER, ascending id inside a group; seeds are POSITIONS of rows).  sizes int64 [G] on the
+ * HOST: sizes[g] = off[g + 1] - off[g] (the caller keeps the two in agreement; the workspace is
+ * sized from it).  Inside one group of n_g rows:
+ *
+ *   M[c][i]   = max(0, ||f_i||^2 + key(i, c)), the squared distance from centre c to point i;
+ *               key(i, c) = ||f_c||^2 - 2 f_i . f_c is dd_nn_same_class's key (the dot product on
+ *               split MFMA, hi.hi + hi.lo + lo.hi of the `operands` halves with the centre as the
+ *               first factor, fp32 accumulation, K order fixed by D; the norms in fp32 in an order
+ *               fixed by D).  M[c][c] = 0.  Only rows M[c][.] are ever read: a centre's row serves
+ *               the seeds, the fold and the gain alike, so every distance has one source (M is not
+ *               symmetric bit for bit, and need not be).  On small-integer rows every entry is
+ *               exact.
+ *   cur[i]    = min over the kept rows c of M[c][i]; -1 for a kept row; +inf in a group that
+ *               keeps nothing.
+ *   step t of group g (t < picks[g]): for every not-yet-kept row j
+ *               gain_j = sum_i max(cur[i] - M[j][i], 0)
+ *               over the group's rows in fp32 (a kept row adds max(-1 - M, 0) = 0).  The order:
+ *               lane l of the wave that owns j takes positions l, l + 64, ... of the group
+ *               ascending in one add chain, then a fixed butterfly; it depends on n_g alone.
+ *               The row with the largest gain is taken, a tie to the smaller id (a gain of 0 is
+ *               still a pick: quotas are always met):
+ *               picked[t][g] = its id,  gain[t][g] = its gain,  then cur = min(cur, M[pick][.])
+ *   and (t, g) with t >= picks[g]: picked = -1, gain = -1.  cur fp32 [n] (written, in the order
+ *   of `rows`) is the final cur; a row outside every group has +inf.
+ *   bad[0] += the rows with a NaN or infinite element (the caller clears it, and rejects the
+ *   call's results when it is non-zero).
+ *
+ * Launches (all on `stream`, nothing read back, no allocation): the pack of the rows into operand
+ * halves; the distance matrices, once (workgroups of 128 points x 128-centre steps; row c of
+ * group g at float moff[g] + c pitch_g, pitch_g = n_g rounded up to a multiple of 64, the tail
+ * +0); ceil(max_seeds / S) seed launches (S = seed_batch, 0: 8); steps + 1 pick launches, launch
+ * t folding the row that launch t - 1 published into an LDS copy of cur (n_g floats), streaming
+ * the unkept rows of M against it (n_g^2 4 bytes per group and pick: the whole cost) and
+ * publishing one candidate per workgroup with a 64-bit atomic maximum on (bits(gain) << 32) |
+ * ~position into slot [t][g]; cur is double-buffered by the parity of t and a workgroup writes
+ * only its own slice of the next buffer; one finish.  The launch boundaries are the only ordering
+ * between workgroups.  `blocks`: workgroups per group of the seed and pick launches (0: from the
+ * largest group and G alone).
+ *
+ * Invariance: an entry of M is a function of the two rows and D alone, a gain of the group's rows
+ * in id order, and min / max are order-independent, so every output is bitwise independent of
+ * seed_batch, blocks, the rows' placement, the other groups and their layout, and of whether a
+ * centre arrives as a seed or as a pick.
+ *
+ * Limits: 0 <= n < 2^31, 1 <= D <= 4096, 1 <= G <= DD_KCENTER_MAX_GROUPS, 0 <= sizes[g] <=
+ * DD_KMEDOIDS_MAX_GROUP_ROWS (64 KiB of LDS hold a group's cur), sum sizes <= n, 0 <= steps,
+ * max_seeds <= n, 0 <= seed_batch <= DD_KCENTER_MAX_SEED_BATCH, 0 <= blocks <=
+ * DD_KCENTER_MAX_BLOCKS, operands DD_OPERANDS_F16X3 or DD_OPERANDS_BF16X3; outside them, a NULL
+ * buffer the call would touch or a workspace below dd_kmedoids_workspace_bytes or not 16-byte
+ * aligned is DD_EINVAL with a message before any launch.  n == 0 returns DD_OK.  The workspace
+ * (host only; 0 for bad arguments) holds the halves, 4 n pad16(D) bytes, 4 n bytes of norms,
+ * 8 (G + 1) bytes of offsets, sum_g 4 n_g pitch_g bytes of matrices, 8 n bytes of cur and
+ * 8 max(steps, 1) G bytes of slots, each region rounded up to 256.
+ * ---------------------------------------------------------------------------------------- */
+#define DD_KMEDOIDS_MAX_GROUP_ROWS 16384
+
+size_t dd_kmedoids_workspace_bytes(int64_t n, int32_t D, int32_t G, const int64_t* sizes,
+                                   int64_t steps, int32_t operands);
+
+int dd_kmedoids_greedy(const float* rows, const int64_t* ids, int64_t n, int32_t D,
+                       const int64_t* off, const int64_t* sizes, int32_t G, const int64_t* seeds,
+                       const int64_t* seed_off, int64_t max_seeds, const int64_t* picks,
+                       int64_t steps, int32_t operands, int32_t seed_batch, int32_t blocks,
+                       int64_t* picked, float* gain, float* cur, int32_t* bad, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------- *
  * Distance to the nearest k-means centroid in feature space: the self-supervised prototype
  * distance of Sorscher et al. ("Beyond neural scaling laws"), which needs no labels.  Purely
  * additive: dd_abi_version() stays 10.
