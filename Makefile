@@ -23,8 +23,11 @@ all: $(LIB)
 # they differ in register allocation and scheduling only; 188 registers, no spills, either way),
 # so no result depends on it and it can go when the advisory does.  The host pass of hipcc notes
 # "not a recognized feature" for it: harmless, -Xarch_device takes no option with an argument.
+# dd_maha.hip is guarded for the same reason: its centring (a = f - mu, eight independent fp32
+# subtractions per staging step, on which the scatter's exact-equality claim rests) is the shape
+# of loop a compiler packs in pairs.
 # The older units keep the flags their recorded results and timings were taken with.
-$(OBJDIR)/dd_kmeans.o $(OBJDIR)/dd_kmedoids.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+$(OBJDIR)/dd_kmeans.o $(OBJDIR)/dd_kmedoids.o $(OBJDIR)/dd_maha.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(OBJDIR)/%.o: data_diet_distributed_amd/csrc/%.hip $(HDR)
 	@mkdir -p $(OBJDIR)

@@ -52,6 +52,7 @@ EXPORTS = (
     "dd_kcenter_workspace_bytes", "dd_kcenter_seed_batch", "dd_kcenter_greedy",
     "dd_kmedoids_workspace_bytes", "dd_kmedoids_greedy",
     "dd_kmeans_workspace_bytes", "dd_kmeans_assign", "dd_kmeans_centroids",
+    "dd_maha_workspace_bytes", "dd_maha_segment_rows", "dd_maha_scatter", "dd_maha_dist",
 )
 
 
@@ -120,6 +121,10 @@ def lib():
                 "dd_kmeans_assign": (I32, [P, I64, P, I32, I32, I32, I32, P, P, P, P, P, P, P,
                                            SZ, P]),
                 "dd_kmeans_centroids": (I32, [P, P, I32, I32, P, P]),
+                "dd_maha_workspace_bytes": (SZ, [I64, I32, I32]),
+                "dd_maha_segment_rows": (I64, [I64, I32]),
+                "dd_maha_scatter": (I32, [P, P, P, P, I64, I32, I64, I32, P, P, P, SZ, P]),
+                "dd_maha_dist": (I32, [P, P, P, P, I64, I32, I64, P, I32, P, P, P, SZ, P]),
                 "dd_conv_pegrad_method": (I32, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_workspace_bytes": (SZ, [ctypes.POINTER(ConvGeom), I32, I32]),
                 "dd_conv_pegrad_sqnorm": (I32, [P, P, ctypes.POINTER(ConvGeom), P, I32, I32, P,
@@ -933,6 +938,99 @@ def kmeans_centroids(sums: torch.Tensor, counts: torch.Tensor, centroids: torch.
                                    _stream(centroids))
     _check(rc, "dd_kmeans_centroids")
     return centroids
+
+
+# ---- Mahalanobis distance to the class mean (tied covariance) -----------------------------------
+def maha_workspace_bytes(n: int, D: int, operands: str = "f16x3") -> int:
+    """Bytes of the workspace of maha_scatter / maha_dist on n rows (dd_maha_workspace_bytes; 0
+    for sizes outside the entry points' limits)."""
+    return int(lib().dd_maha_workspace_bytes(int(n), int(D), OPERANDS[operands]))
+
+
+def maha_segment_rows(n: int, D: int) -> int:
+    """Rows per segment of maha_scatter's sum over n rows (dd_maha_segment_rows): the length of
+    the longest fp32 accumulation behind an entry of S."""
+    return int(lib().dd_maha_segment_rows(int(n), int(D)))
+
+
+def _maha_args(what, rows, labels, counts, mean, operands, workspace):
+    """The checks maha_scatter and maha_dist share.  Returns (n, D, C, code, workspace)."""
+    _dev(rows, torch.float32, "rows", 2)
+    _dev(mean, torch.float32, "mean", 2)
+    n, D = rows.shape
+    C = mean.shape[0]
+    if mean.shape[1] != D:
+        raise ValueError(f"mean must be [C, {D}] (got {tuple(mean.shape)})")
+    if labels.numel() != n:
+        raise ValueError("labels must have n entries")
+    if counts.numel() != C:
+        raise ValueError(f"counts must have C = {C} entries (got {counts.numel()})")
+    code = _operands_code(operands)
+    need = int(lib().dd_maha_workspace_bytes(n, D, code))
+    if need == 0:
+        raise ValueError(f"{what}: unsupported size n={n}, D={D}")
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    return n, D, C, code, workspace
+
+
+def maha_scatter(rows: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor,
+                 mean: torch.Tensor, *, operands: str = "f16x3", out=None, bad=None,
+                 workspace=None):
+    """The within-class scatter S = sum_i a_i a_i^T, a_i = rows[i] - mean[labels[i]], of rows
+    [n, D] in dataset order (dd_maha_scatter): float64 [D, D], exactly symmetric.  counts int64
+    [C] (class_counts of the same rows: the only row of a class adds nothing) and mean fp32
+    [C, D] (class_centroids).  bad int64 [1] accumulates the rows with a NaN or an infinite
+    element (None: a zeroed one is made).  workspace: a uint8 tensor of maha_workspace_bytes, or
+    None to allocate one.  Returns (S, bad, workspace)."""
+    n, D, C, code, workspace = _maha_args("maha_scatter", rows, labels, counts, mean, operands,
+                                          workspace)
+    if out is None:
+        out = torch.empty((D, D), dtype=torch.float64, device=rows.device)
+    if bad is None:
+        bad = torch.zeros(1, dtype=torch.int64, device=rows.device)
+    e0 = _t0(rows, always=True)
+    rc = lib().dd_maha_scatter(
+        _opt(rows if n else None, torch.float32, "rows"),
+        _opt(labels if n else None, torch.int64, "labels"), _dev(counts, torch.int64, "counts"),
+        _dev(mean, torch.float32, "mean"), n, D, C, code, _opt(out, torch.float64, "out", D * D),
+        _dev(bad, torch.int64, "bad"), _dev(workspace, torch.uint8, "workspace"),
+        workspace.numel() * workspace.element_size(), _stream(rows))
+    _check(rc, "dd_maha_scatter")
+    # the fp32 rows read once (and once more for the non-finite count), S written once
+    _t1(e0, "el2n", 8.0 * n * D + 8.0 * D * D, rows)
+    return out, bad, workspace
+
+
+def maha_dist(rows: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor,
+              mean: torch.Tensor, W: torch.Tensor, *, operands: str = "f16x3", dist=None,
+              accum=None, workspace=None):
+    """|| W (rows[i] - mean[labels[i]]) ||_2 per row of rows [n, D], any n of the dataset's rows
+    (dd_maha_dist).  W fp32 [D, D] lower triangular (zeros above the diagonal); counts / mean of
+    the WHOLE dataset as for maha_scatter.  Writes dist fp32 [n] and / or adds to accum fp32 [n];
+    NaN for a label outside [0, C) or a non-finite element, exactly 0 for the only row of a
+    class.  Returns the workspace."""
+    n, D, C, code, workspace = _maha_args("maha_dist", rows, labels, counts, mean, operands,
+                                          workspace)
+    _dev(W, torch.float32, "W", 2)
+    if tuple(W.shape) != (D, D):
+        raise ValueError(f"W must be [{D}, {D}] (got {tuple(W.shape)})")
+    if dist is None and accum is None:
+        raise ValueError("maha_dist: no output requested")
+    ptrs = [_opt(dist, torch.float32, "dist", n), _opt(accum, torch.float32, "accum", n)]
+    if n == 0:  # nothing to do (and an empty tensor's pointer is NULL: "not requested")
+        return workspace
+    e0 = _t0(rows, always=True)
+    rc = lib().dd_maha_dist(
+        _dev(rows, torch.float32, "rows"), _dev(labels, torch.int64, "labels", 1),
+        _dev(counts, torch.int64, "counts"), _dev(mean, torch.float32, "mean"), n, D, C,
+        _dev(W, torch.float32, "W"), code, *ptrs, _dev(workspace, torch.uint8, "workspace"),
+        workspace.numel() * workspace.element_size(), _stream(rows))
+    _check(rc, "dd_maha_dist")
+    # the fp32 rows and W read once, their halves written once and read once
+    Dp = (D + 15) // 16 * 16
+    _t1(e0, "el2n", (n + D) * (4.0 * D + 8.0 * Dp), rows)
+    return workspace
 
 
 def label_counter(device) -> torch.Tensor:

@@ -21,12 +21,14 @@ DEFAULTS = {
     # (the mean distance to the knn_k nearest other examples of any class and the share of them
     # with another label, scoring.KNN_METHODS) | kmeans (the distance to the nearest centroid of
     # a k-means clustering of the feature rows: the prototype distance without labels,
-    # scoring.CLUSTER_METHODS); select_by takes any
+    # scoring.CLUSTER_METHODS) | maha (the Mahalanobis distance to the class mean under the tied
+    # within-class covariance of the feature rows, scoring.COVARIANCE_METHODS); select_by takes any
     "score_methods": ["el2n"],
     "select_by": "el2n",
     "knn_k": 5,                       # neighbours of knn / knn_disagree (1..16)
     "kmeans_k": 0,                    # clusters of kmeans (0: num_classes; at most 4096)
     "kmeans_iters": 20,               # Lloyd updates of kmeans per checkpoint (1..1000)
+    "maha_shrink": 0.01,              # shrinkage of maha's covariance to its mean eigenvalue [0, 1]
     "select_policy": "global",        # global (reference) | stratified | balanced class quotas
     "select_skip": 0,                 # ranks skipped from the top before the k kept ones
     "select_fill": "score",           # score (the rank cut) | kcenter (coverage: greedy k-center)

@@ -1,15 +1,15 @@
 """The consumers of the EL2N pass's train-BN forward: LogitScores (el2n + LOGIT_METHODS, from
-each launch's logits), ProtoScore, KMeansScore, NNScore and KNNScore (from the checkpoint's pooled
-feature rows, over every rank), and ForwardScores, which holds the requested ones for one
-score_shard call.
+each launch's logits), ProtoScore, KMeansScore, NNScore, KNNScore and MahaScore (from the
+checkpoint's pooled feature rows, over every rank), and ForwardScores, which holds the requested
+ones for one score_shard call.
 
 The pass hands every launch's logits to `consume` and, when `features` is not None, writes the
 launch's feature rows there; after a checkpoint's last chunk it calls `end_checkpoint`.  Every
 rank issues its collectives in the same order: the counts all-reduce (proto) and the lengths and
-labels all-gathers (nn and the knn scores: one of each, shared, GatheredRows; kmeans alone takes
-the lengths only) at construction, then per checkpoint the proto all-reduce, the kmeans
+labels all-gathers (nn, the knn scores and maha: one of each, shared, GatheredRows; kmeans alone
+takes the lengths only) at construction, then per checkpoint the proto all-reduce, the kmeans
 all-reduces (the seed rows, then one per Lloyd iteration) and last the one all-gather of the
-feature rows that nn and the knn scores share.
+feature rows that nn, the knn scores and maha share.
 """
 from __future__ import annotations
 
@@ -158,6 +158,65 @@ def kmeans(features: torch.Tensor, k: int, iters: int, operands: str = "f16x3"):
         raise ValueError(f"kmeans: {int(bad.item())} feature row(s) with a NaN, an infinite or an "
                          f"|v| >= 2^15 element: their distance is undefined")
     return centroids, assign, dist
+
+
+def class_means(features: torch.Tensor, labels: torch.Tensor, counts: torch.Tensor, order=None):
+    """(mean fp32 [C, D], bad_feat int32 [C]) of `features` [N, D], every row of the dataset:
+    proto's class means (dd_class_feature_sums -> dd_class_centroids: the exact fixed-point sums,
+    the same rounding) and its per-class counts of rows with a NaN, an infinite or an
+    |v| >= 2^15 element."""
+    C, D = counts.numel(), features.shape[1]
+    sums = torch.zeros((C, D), dtype=torch.int64, device=features.device)
+    bad_feat = torch.zeros(C, dtype=torch.int32, device=features.device)
+    _capi.class_feature_sums(features, labels, sums, bad_feat, order=order)
+    return _capi.class_centroids(sums, counts, bad_feat), bad_feat
+
+
+def maha_whitener(S: torch.Tensor, N: int, shrink: float) -> torch.Tensor:
+    """W fp32 [D, D] on S's device, lower triangular with W Sigma W^T = I for Sigma = S / N +
+    shrink (trace(S / N) / D) I: the float64 algebra between dd_maha_scatter and dd_maha_dist, on
+    the host (one D x D copy each way; not a hot path).  Raises ValueError if Sigma has no
+    Cholesky factor."""
+    sigma = S.detach().to("cpu", torch.float64) / float(N)
+    D = sigma.shape[0]
+    sigma.diagonal().add_(float(shrink) * float(sigma.diagonal().sum()) / D)
+    L, info = torch.linalg.cholesky_ex(sigma)
+    if int(info) or not bool(torch.isfinite(L).all()):
+        raise ValueError(f"maha: the covariance is not positive definite at maha_shrink={shrink} "
+                         f"(N={N} rows, D={D}): raise maha_shrink")
+    W = torch.linalg.solve_triangular(L, torch.eye(D, dtype=torch.float64), upper=False)
+    return torch.tril(W).to(torch.float32).to(S.device)
+
+
+def check_maha_rows(bad_feat: torch.Tensor, nonfinite: torch.Tensor):
+    """One read of the two counters: reject feature rows the class means or the scatter cannot
+    take, naming how many."""
+    bad, nf = int(bad_feat.sum().item()), int(nonfinite.item())
+    if bad or nf:
+        raise ValueError(f"maha: {max(bad, nf)} feature row(s) with a NaN, an infinite or an "
+                         f"|v| >= 2^15 element ({nf} non-finite): the covariance is undefined")
+
+
+def maha(rows: torch.Tensor, labels: torch.Tensor, num_classes: int, shrink: float = 0.01,
+         operands: str = "f16x3") -> torch.Tensor:
+    """fp32 [n]: each row's Mahalanobis distance to its class mean under the tied within-class
+    covariance of `rows` [n, D] (include/dd_capi.h dd_maha_scatter), shrunk by `shrink` towards
+    its mean eigenvalue; exactly 0 for the only row of a class.  Raises LabelError for a label
+    outside [0, C) and ValueError for a row with a NaN, an infinite or an |v| >= 2^15 element or a
+    covariance without a Cholesky factor (maha_shrink too small)."""
+    from .methods import check_shrink
+    shrink = check_shrink(shrink)
+    _check_width("maha", rows.shape[1])
+    labels = labels.contiguous()
+    counts, _ = _capi.class_counts(labels, num_classes, check=True)
+    check_class_sizes(int(counts.max().item()))
+    mean, bad_feat = class_means(rows, labels, counts)
+    S, nonfinite, ws = _capi.maha_scatter(rows, labels, counts, mean, operands=operands)
+    check_maha_rows(bad_feat, nonfinite)
+    W = maha_whitener(S, rows.shape[0], shrink)
+    dist = torch.empty(rows.shape[0], dtype=torch.float32, device=rows.device)
+    _capi.maha_dist(rows, labels, counts, mean, W, operands=operands, dist=dist, workspace=ws)
+    return dist
 
 
 def ensemble_mean(acc: torch.Tensor, K: int) -> torch.Tensor:
@@ -404,6 +463,56 @@ class KNNScore:
         return {m: ensemble_mean(a, K) for m, a in self.acc.items()}
 
 
+class MahaScore:
+    """The per-call state of the maha score for the shard's `labels` [n], built once and reused by
+    every checkpoint: every rank's labels (`rows`), their class counts (`bad` is this shard's
+    count of labels outside [0, C)) and label-sorted order, the accumulator and the kernels'
+    workspace.  Every rank forms the class means and the scatter from ALL the gathered rows in
+    dataset order and factors the same matrix, so nothing floating-point is reduced across ranks
+    and the scores do not depend on the chunk size, the lanes or the world size.  With `proto`
+    (the call's ProtoScore, when that score is requested too) the class means are not formed a
+    second time: its `centroids` and `bad_feat` of the checkpoint are read (the same kernels on
+    the same exact sums: the same bits)."""
+
+    def __init__(self, labels: torch.Tensor, linear, rows: GatheredRows, operands: str,
+                 shrink: float, proto: Optional["ProtoScore"] = None):
+        n, dev = labels.numel(), labels.device
+        C, D = linear.out_features, linear.in_features
+        _check_width("maha", D)
+        self.operands, self.shrink, self.proto = operands, float(shrink), proto
+        self.labels, self.all_labels = labels, rows.labels.contiguous()
+        self.N = self.all_labels.numel()
+        _, self.bad = _capi.class_counts(labels, C, check=False)
+        self.counts, _ = _capi.class_counts(self.all_labels, C, check=False)
+        if self.N >= _capi.PROTO_MAX_CLASS:  # (the class means' fixed-point sums: proto's limit)
+            check_class_sizes(int(self.counts.max().item()))
+        self.order = torch.argsort(self.all_labels, stable=True)
+        self.accum = torch.zeros(n, dtype=torch.float32, device=dev)
+        need = _capi.maha_workspace_bytes(self.N, D, operands)
+        self.workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+
+    def end_checkpoint(self, features: torch.Tensor, allf: torch.Tensor):
+        """At the same point of a checkpoint as NNScore's (after ProtoScore's), on the same
+        gathered rows `allf`: the class means (ProtoScore's where it ran) and the scatter over all
+        of them, the host's D x D algebra (which reads S
+        and the two counters back: one synchronisation per checkpoint), and the distance launch
+        over this shard's rows."""
+        if self.proto is not None:
+            mean, bad_feat = self.proto.centroids, self.proto.bad_feat
+        else:
+            mean, bad_feat = class_means(allf, self.all_labels, self.counts, self.order)
+        S, nonfinite, self.workspace = _capi.maha_scatter(
+            allf, self.all_labels, self.counts, mean, operands=self.operands,
+            workspace=self.workspace)
+        check_maha_rows(bad_feat, nonfinite)
+        W = maha_whitener(S, self.N, self.shrink)
+        _capi.maha_dist(features, self.labels, self.counts, mean, W, operands=self.operands,
+                        accum=self.accum, workspace=self.workspace)
+
+    def finalize(self, K: int) -> Dict[str, torch.Tensor]:
+        return {"maha": ensemble_mean(self.accum, K)}
+
+
 class ForwardScores:
     """Everything one score_shard call takes from the EL2N pass: the requested forward scores
     among cfg.methods (a ScoreConfig) for the shard's `labels` [n] and classifier `linear`.
@@ -421,17 +530,20 @@ class ForwardScores:
         self.kcenter_ckpt, self.kcenter_rows, self._ckpts_done = kcenter_ckpt, None, 0
         logit = [m for m in methods if m in LOGIT_FAMILY]
         self.logit = LogitScores(logit, n, labels.device) if logit else None
-        self.proto = self.kmeans = self.nn = self.knn = self.rows = None
+        self.proto = self.kmeans = self.nn = self.knn = self.maha = self.rows = None
         if "proto" in methods:
             self.proto = ProtoScore(labels, linear, group, cfg.batch_size)
         knn = [m for m in methods if m in KNN_METHODS]
-        if "nn" in methods or knn or kcenter_ckpt is not None:
+        if "nn" in methods or knn or "maha" in methods or kcenter_ckpt is not None:
             labels = labels.contiguous()
             self.rows = GatheredRows(labels, group)
         if "nn" in methods:
             self.nn = NNScore(labels, linear, self.rows, cfg.el2n_operands)
         if knn:
             self.knn = KNNScore(knn, labels, linear, self.rows, cfg.el2n_operands, cfg.knn_k)
+        if "maha" in methods:
+            self.maha = MahaScore(labels, linear, self.rows, cfg.el2n_operands, cfg.maha_shrink,
+                                  self.proto)
         if "kmeans" in methods:
             lengths, rank = ((self.rows.lengths, self.rows.rank) if self.rows is not None
                              else shard_lengths(n, group))
@@ -440,7 +552,7 @@ class ForwardScores:
         # the one [n, D] fp32 buffer of the checkpoint's feature rows (n D 4 bytes: 102 MB at
         # 50 000 x 512, 10.5 GB for 1.28 M x 2048 rows on one rank), or None: logits only
         self.features = None
-        by_features = self.proto or self.nn or self.knn or self.kmeans
+        by_features = self.proto or self.nn or self.knn or self.kmeans or self.maha
         if kcenter_ckpt is not None:
             _check_width("kcenter", linear.in_features)
         if by_features or kcenter_ckpt is not None:
@@ -465,9 +577,10 @@ class ForwardScores:
         if self.kmeans is not None:
             self.kmeans.end_checkpoint(self.features)
         keep = self._ckpts_done == self.kcenter_ckpt
-        # one all-gather of the rows serves nn, the knn scores and the kcenter fill (which alone
-        # needs it at its one checkpoint only)
-        if self.rows is not None and (keep or self.nn is not None or self.knn is not None):
+        # one all-gather of the rows serves nn, the knn scores, maha and the kcenter fill (which
+        # alone needs it at its one checkpoint only)
+        if self.rows is not None and (keep or self.nn is not None or self.knn is not None
+                                      or self.maha is not None):
             allf = self.rows.gather(self.features)
             if keep:
                 # (one rank: `allf` is the feature buffer itself, which the next checkpoint
@@ -477,10 +590,12 @@ class ForwardScores:
                 self.nn.end_checkpoint(self.features, allf)
             if self.knn is not None:
                 self.knn.end_checkpoint(self.features, allf)
+            if self.maha is not None:
+                self.maha.end_checkpoint(self.features, allf)
         self._ckpts_done += 1
 
     def _parts(self):
-        return [p for p in (self.logit, self.proto, self.nn, self.knn, self.kmeans)
+        return [p for p in (self.logit, self.proto, self.nn, self.knn, self.kmeans, self.maha)
                 if p is not None]
 
     def tensors(self) -> List[torch.Tensor]:

@@ -43,15 +43,19 @@ from .subset_index import json_radius, write_subset_index
 from .synthetic import state_digest
 
 
-FEATURE_SCORES = ("nn", "knn", "knn_disagree", "kmeans")  # from the rows the classifier consumes
+# from the rows the classifier consumes
+FEATURE_SCORES = ("nn", "knn", "knn_disagree", "kmeans", "maha")
 
 
-def _feature_scores(feats, labels, num_classes, score, knn_k, kmeans_k=0, kmeans_iters=20):
+def _feature_scores(feats, labels, num_classes, score, knn_k, kmeans_k=0, kmeans_iters=20,
+                    maha_shrink=0.01):
     """The chosen score of FEATURE_SCORES among the visited rows `feats` [n, D] (LabelError for
     a label outside [0, C))."""
-    from .forward_scores import kmeans, nearest_k, nearest_same_class
+    from .forward_scores import kmeans, maha, nearest_k, nearest_same_class
     if score == "nn":
         return nearest_same_class(feats, labels, num_classes)
+    if score == "maha":
+        return maha(feats, labels, num_classes, maha_shrink)
     if score == "kmeans":
         _capi.class_counts(labels.contiguous(), num_classes, check=True)
         return kmeans(feats, int(kmeans_k) or num_classes, kmeans_iters)[2]
@@ -70,13 +74,15 @@ def _score_rows(logits, labels, out, bad, score="el2n"):
 
 
 def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect=None,
-                            score="el2n", knn_k=5, keep_rows=False, kmeans_k=0, kmeans_iters=20):
+                            score="el2n", knn_k=5, keep_rows=False, kmeans_k=0, kmeans_iters=20,
+                            maha_shrink=0.01):
     """Scores of every example the loader yields, in visit order, plus the visited indices
     (`score`: "el2n" or one of _capi.LOGIT_STATS, from the same logits; or "nn", the distance to
     the nearest visited example of the same class, or "knn" / "knn_disagree", the mean distance
     to the knn_k nearest visited examples and the share of them with another label, or "kmeans",
     the distance to the nearest of kmeans_k centroids of the visited examples after kmeans_iters
-    Lloyd updates, from the rows `net.linear` consumes).
+    Lloyd updates, or "maha", the Mahalanobis distance to the class mean under the visited
+    examples' tied covariance shrunk by maha_shrink, from the rows `net.linear` consumes).
     A dict given as `collect` receives "labels" (the targets in visit order, int64 on the
     device) and "num_classes" (the width of the logits), for the class selection policies, and
     with keep_rows "rows": the rows `net.linear` consumes, in visit order (the kcenter fill).
@@ -117,7 +123,7 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
             hook.remove()
     if by_rows and visit:
         scores = [_feature_scores(torch.cat(feats).contiguous(), torch.cat(targets), C, score,
-                                  knn_k, kmeans_k, kmeans_iters)]
+                                  knn_k, kmeans_k, kmeans_iters, maha_shrink)]
     if collect is not None and keep_rows:
         collect["rows"] = torch.cat(feats).contiguous() if feats else None
     if collect is not None:
@@ -321,7 +327,7 @@ def fast_path(train_loader, net, device):
 
 
 def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, score="el2n",
-                     knn_k=5, collect=None, kmeans_k=0, kmeans_iters=20):
+                     knn_k=5, collect=None, kmeans_k=0, kmeans_iters=20, maha_shrink=0.01):
     """Scores in visit order + visited indices, like el2n_scores_from_loader, on the hand
     kernels: every visit batch of the loader's BatchSampler (all of size B but a ragged last
     one) is one BN group; chunks of whole batches are gathered + normalised on device.  A dict
@@ -375,7 +381,7 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
             _score_rows(logits.contiguous(), lab_d[idx], scores[c0:c1], bad, score)
         if by_rows:  # neighbours among the visited examples (LabelError inside)
             return _feature_scores(feats, lab_d[visit_d], model.linear.out_features, score,
-                                   knn_k, kmeans_k, kmeans_iters), visit_d
+                                   knn_k, kmeans_k, kmeans_iters, maha_shrink), visit_d
     # a label outside [0, C): the reference's one_hot raises (:17), so does this path
     _capi.check_labels(bad, model.linear.out_features, "sparse_loader")
     return scores, visit_d
@@ -427,7 +433,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                   *, dataset=None, subset_index_path=None, return_indices=False,
                   fast: bool = True, refine="auto", policy="global", skip=0, score="el2n",
                   knn_k=5, fill="score", seed_frac=0.0, kmeans_k=0, kmeans_iters=20,
-                  objective="radius"):
+                  objective="radius", maha_shrink=0.01):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
@@ -453,6 +459,9 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     _capi.KMEANS_MAX_K) of a k-means clustering of the visited examples' rows, kmeans_iters Lloyd
     updates from evenly spaced visited rows (dd_kmeans_assign; fewer visited examples than
     clusters raise).
+    "maha" ranks by the Mahalanobis distance to the class mean under the tied within-class
+    covariance of the visited examples' rows, shrunk by maha_shrink in [0, 1] towards its mean
+    eigenvalue (dd_maha_scatter / dd_maha_dist; a covariance without a Cholesky factor raises).
     fill / seed_frac: how the quotas are filled (ScoreConfig.select_fill / kcenter_seed_frac):
     "score" is the rank cut; "kcenter" seeds every group with its top
     max(1, floor(seed_frac * quota)) examples by `score` and picks the rest by farthest-first
@@ -467,7 +476,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
     over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
     score="el2n"."""
-    from .methods import check_objective, check_selection
+    from .methods import check_objective, check_selection, check_shrink
     from .scoring import normalize_refine, select_with_policy
     refine = normalize_refine(refine)
     if score in ("variability", "grand", "proto"):
@@ -485,6 +494,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                                 ("kmeans_iters", kmeans_iters, 1, 1000)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
                 raise ValueError(f"{name} must be an integer in {lo}..{hi} (got {v!r})")
+    if score == "maha":
+        maha_shrink = check_shrink(maha_shrink)
     if refine is True and score != "el2n":
         raise ValueError("refine=True re-scores EL2N only: it needs score='el2n'")
     skip = check_selection(policy, skip, "policy", "skip", fill=fill, seed_frac=seed_frac,
@@ -507,13 +518,14 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     if fp is not None:
         scores, visit = el2n_scores_fast(train_loader, fp[0], fp[1], device, score=score,
                                          knn_k=knn_k, collect=seen, kmeans_k=kmeans_k,
-                                         kmeans_iters=kmeans_iters)
+                                         kmeans_iters=kmeans_iters, maha_shrink=maha_shrink)
     else:
         if policy != "global":  # a class policy needs the visited targets
             seen = {}
         scores, visit = el2n_scores_from_loader(train_loader, net, device, collect=seen,
                                                 score=score, knn_k=knn_k, keep_rows=kcenter,
-                                                kmeans_k=kmeans_k, kmeans_iters=kmeans_iters)
+                                                kmeans_k=kmeans_k, kmeans_iters=kmeans_iters,
+                                                maha_shrink=maha_shrink)
     samples = _capi.keep_count(train_samples, sparsity)
     if samples < 0 or samples > scores.numel():
         raise ValueError(f"keep count {samples} outside [0, {scores.numel()}]")
@@ -557,6 +569,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                             # (the resolved cluster count, as score.py records it)
                             **({"kmeans_k": int(kmeans_k) or int(module.linear.out_features),
                                 "kmeans_iters": int(kmeans_iters)} if score == "kmeans" else {}),
+                            **({"maha_shrink": float(maha_shrink)} if score == "maha" else {}),
                             **({} if default_rule else {
                                 "select_policy": policy, "select_skip": int(skip),
                                 "class_quota": sparse_loader.last_selection["class_quota"],

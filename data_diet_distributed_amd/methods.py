@@ -42,18 +42,36 @@ KNN_METHODS = ("knn", "knn_disagree")
 # atypical).  The cluster sums are exact fixed point like proto's, so the scores are bitwise
 # independent of chunks, lanes and ranks (include/dd_capi.h dd_kmeans_assign).
 CLUSTER_METHODS = ("kmeans",)
+# proto's distance in the metric of the rows' own tied (within-class) covariance (Lee et al. 2018;
+# shrinkage lambda = ScoreConfig.maha_shrink), from the same feature rows over the WHOLE dataset:
+#   maha_i = || L^-1 (f_i - mu_{y_i}) ||_2,  L L^T = S / N + lambda (tr(S / N) / D) I,
+#   S = sum_i (f_i - mu_{y_i}) (f_i - mu_{y_i})^T
+# (larger = more atypical; no handful of high-variance channels carries the distance).  Every rank
+# forms S from all the rows in dataset order, so the scores are bitwise independent of chunks,
+# lanes and ranks (include/dd_capi.h dd_maha_scatter).
+COVARIANCE_METHODS = ("maha",)
 
 
 def known(method: str) -> bool:
     return (method == "grand" or method in FORWARD_SCORES or method in KNN_METHODS
-            or method in CLUSTER_METHODS)
+            or method in CLUSTER_METHODS or method in COVARIANCE_METHODS)
 
 
 def pass_of(method: str) -> str:
     """The pass that computes `method`: "el2n" (the shared forward of the logit family, the
-    feature scores, the neighbour scores and the cluster score) or "grand"."""
+    feature scores, the neighbour scores, the cluster score and the covariance score) or
+    "grand"."""
     return ("el2n" if method in FORWARD_SCORES or method in KNN_METHODS
-            or method in CLUSTER_METHODS else "grand")
+            or method in CLUSTER_METHODS or method in COVARIANCE_METHODS else "grand")
+
+
+def check_shrink(shrink, name="maha_shrink") -> float:
+    """ScoreConfig's maha_shrink, and sparse_loader's under its own name: a number in [0, 1]
+    (returned as a float)."""
+    if (isinstance(shrink, bool) or not isinstance(shrink, (int, float, np.integer, np.floating))
+            or not 0.0 <= float(shrink) <= 1.0):
+        raise ValueError(f"{name} must be a number in [0, 1] (got {shrink!r})")
+    return float(shrink)
 
 
 def refinable(method: str) -> bool:

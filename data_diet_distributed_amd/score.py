@@ -145,6 +145,7 @@ def engine_config(cfg):
                        knn_k=int(cfg.get("knn_k", 5)),
                        kmeans_k=int(cfg.get("kmeans_k", 0)),
                        kmeans_iters=int(cfg.get("kmeans_iters", 20)),
+                       maha_shrink=cfg.get("maha_shrink", 0.01),
                        select_fill=str(cfg.get("select_fill", "score")),
                        kcenter_seed_frac=float(cfg.get("kcenter_seed_frac", 0.0)),
                        kcenter_ckpt=int(cfg.get("kcenter_ckpt", -1)),
@@ -200,6 +201,8 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
             meta["knn_k"] = int(ecfg.knn_k)  # (a run without them: metadata unchanged)
         if "kmeans" in ecfg.methods:
             meta.update(kmeans_k=int(ecfg.kmeans_k) or ncls, kmeans_iters=int(ecfg.kmeans_iters))
+        if "maha" in ecfg.methods:
+            meta["maha_shrink"] = float(ecfg.maha_shrink)
         sel = eng.last_selection
         if sel["policy"] != "global" or sel["skip"]:  # (a default run's metadata is unchanged)
             meta.update(select_policy=sel["policy"], select_skip=sel["skip"],

@@ -48,10 +48,10 @@ from .collectives import (_all_reduce_sum, _world, all_shards, gather_padded,  #
                           gather_rows, gather_scores, shard_bounds, shard_lengths, world_of)
 from .forward_scores import (ForwardScores, check_class_sizes,  # noqa: F401
                              check_no_singleton_class, ensemble_mean, nearest_same_class)
-from .methods import (CLUSTER_METHODS, FEATURE_METHODS, FORWARD_FAMILY,  # noqa: F401
-                      FORWARD_SCORES, KNN_METHODS, LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS,
+from .methods import (CLUSTER_METHODS, COVARIANCE_METHODS, FEATURE_METHODS,  # noqa: F401
+                      FORWARD_FAMILY, FORWARD_SCORES, KNN_METHODS, LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS,
                       SELECT_FILLS, SELECT_POLICIES, check_fill, check_objective,
-                      check_selection, known, pass_of, refinable, seed_counts)
+                      check_selection, check_shrink, known, pass_of, refinable, seed_counts)
 from .resnet import ResNet
 
 MEAN = (0.4914, 0.4822, 0.4465)  # reference data/loader.py:10
@@ -69,12 +69,17 @@ class ScoreConfig:
     # any class, and the share of them that carry another label)
     # + CLUSTER_METHODS ("kmeans": the distance to the nearest centroid of a k-means clustering of
     # the whole dataset's feature rows: the prototype distance without labels)
+    # + COVARIANCE_METHODS ("maha": the Mahalanobis distance to the class mean under the tied
+    # within-class covariance of the whole dataset's feature rows)
     methods: Sequence[str] = ("el2n",)
     select_by: str = "el2n"                  # which ensemble score ranks the keep-set
     knn_k: int = 5                           # neighbours of the KNN_METHODS (1.._capi.KNN_MAX_K)
     kmeans_k: int = 0                        # clusters of "kmeans" (0: the classifier's class
     #                                          count; at most _capi.KMEANS_MAX_K)
     kmeans_iters: int = 20                   # Lloyd updates per checkpoint (1..1000)
+    # shrinkage of "maha"'s covariance towards its mean eigenvalue, in [0, 1]: Sigma = S / N +
+    # maha_shrink (trace(S / N) / D) I (0 needs more rows than N - C > D for a Cholesky factor)
+    maha_shrink: float = 0.01
     batch_size: int = 128                    # EL2N batch partition (config.yaml:7 batch_size)
     el2n_bn: str = "batch"                   # "batch" = reference semantics; "running" = eval
     grand_batch: int = 1024                  # GraNd chunk (eval BN: any size, same result)
@@ -180,6 +185,8 @@ class ScoreConfig:
                 if (isinstance(v, bool) or not isinstance(v, (int, np.integer))
                         or not lo <= v <= hi):
                     raise ValueError(f"{name} must be an integer in {lo}..{hi} (got {v!r})")
+        if any(m in COVARIANCE_METHODS for m in self.methods):
+            self.maha_shrink = check_shrink(self.maha_shrink)
         if self.el2n_bn not in ("batch", "running"):
             raise ValueError("el2n_bn must be 'batch' or 'running'")
         if self.pegrad_method not in _capi.METHODS:
@@ -857,7 +864,7 @@ class ScoringEngine:
         range).  run() passes check=False and checks the gathered vectors instead (_validate),
         so that on W > 1 ranks every rank raises (or falls back) together.
 
-        "proto", "kmeans", "nn" and the knn scores are those for which a shard is not a slice of
+        "proto", "kmeans", "maha", "nn" and the knn scores are those for which a shard is not a slice of
         the whole: the class prototypes and the k-means centroids are means over every rank's
         rows, and a row's nearest neighbours may lie on another rank.  run() passes its process `group`, over which forward_scores
         issues their collectives; a direct call without a group takes them over [lo, hi) only."""

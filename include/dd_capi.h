@@ -655,6 +655,79 @@ int dd_proto_scores(const float* feat, const int64_t* labels, const float* centr
                     int32_t D, int64_t C, float* score, float* accum, void* stream);
 
 /* ---------------------------------------------------------------------------------------- *
+ * Mahalanobis distance to the class mean with a tied (within-class) covariance: proto's distance
+ * measured in the metric of the feature rows' own covariance (Lee et al. 2018), so that a few
+ * high-variance channels do not carry every distance.  Purely additive: dd_abi_version() stays 10.
+ *
+ * Per checkpoint, over the whole dataset's rows f_i fp32 [D] (N of them) with labels y_i:
+ *   mu_c    the class mean exactly as above: dd_class_feature_sums -> dd_class_centroids, the
+ *           same fixed-point sums, the same rounding to fp32 (`mean` below IS that buffer)
+ *   a_i   = f_i - mu_{y_i}, one fp32 subtraction per element; exact zeros for the only row of a
+ *           class (counts[y_i] == 1) and for a label outside [0, C)
+ *   S     = sum_i a_i a_i^T (D x D): the within-class scatter.  The rows are centred by class
+ *           BEFORE the product, so nothing is cancelled afterwards (sum f f^T - sum n_c mu mu^T
+ *           would subtract two numbers ||mu||^2 / var larger than their difference)
+ *   Sigma = S / N + lambda (trace(S / N) / D) I, lambda = the caller's shrinkage in [0, 1]
+ *   Sigma = L L^T (float64 Cholesky), W = L^-1 (lower triangular), rounded once to fp32
+ *   maha_i = || W a_i ||_2                    (larger = more atypical)
+ * The D x D float64 algebra from S to W is the caller's (once per checkpoint, not a hot path).  A
+ * class with one row scores exactly 0 and adds nothing to S; an empty class is legal.
+ *
+ * dd_maha_scatter: rows fp32 [n][D] in DATASET ORDER (4-byte alignment suffices), labels int64
+ *   [n], counts int64 [C] (dd_class_counts over the same rows), mean fp32 [C][D]; writes S
+ *   float64 [D][D] (exactly symmetric) and ADDS to bad int64 [1] (the caller clears it) the
+ *   number of rows with a NaN or an infinite element (S is then meaningless).  A^T A on split
+ *   MFMA (hi.hi + hi.lo + lo.hi of the `operands` halves, 32x32x16, fp32 accumulation), the
+ *   MFMA's K dimension being the row index.  Only the upper-triangular 128 x 128 output tiles are
+ *   computed.  The rows are cut into segments of dd_maha_segment_rows(n, D) rows (a function of
+ *   n and D alone, a multiple of 32, at least 256 and at most 8192, so the bound below does not
+ *   grow with n); workgroup (tile, segment) stages 32 rows of
+ *   the tile's two column slabs at a time into LDS, centring and splitting on the way in, adds
+ *   the rows of its segment in ascending order and writes an fp32 partial tile to the
+ *   workspace; a reducer adds a tile's partials over the segments in ascending order in float64
+ *   and mirrors the lower triangle.  Columns past D and rows past n contribute exact zeros.
+ *   Each entry: | S_kl - float64 | <= (e_op + (segment_rows + 2) 2^-24) sum_i |a_ik| |a_il|,
+ *   e_op = 2^-22 (f16x3) or 2^-16 (bf16x3).  S depends on the rows, their order, n and D alone.
+ *   n == 0 writes zeros.
+ *
+ * dd_maha_dist: rows / labels / counts / mean as above for ANY n of the dataset's rows (counts
+ *   and mean remain those of the whole dataset), W fp32 [D][D] lower triangular: its entries
+ *   above the diagonal must be zero (whole 64-column chunks above the diagonal of a 128-row
+ *   block are never read).  dist / accum fp32 [n], either may be NULL but not both:
+ *   dist[i] = sqrt(sum_j y_j^2), y = W a_i on split MFMA as above; accum[i] += dist[i].  The
+ *   rows are centred and split once into the workspace; a workgroup takes 128 rows and streams
+ *   W's halves through LDS, one block of 128 outputs at a time, skipping the chunks above the
+ *   diagonal (about half of the products); every y_j is squared and added to a per-row fp32
+ *   register in an order fixed by D, and W a_i is never stored.  NaN for a label outside [0, C)
+ *   or a non-finite element.  Each output depends on its row, the row's class mean, W and D
+ *   alone: bitwise independent of n, of the row's position and of the buffers' alignment.
+ *   | y_j - float64 | <= (e_op + (D + 2) 2^-24) (|W| |a_i|)_j.  n == 0 returns DD_OK.
+ *
+ * Limits: 1 <= D <= 4096, 1 <= C <= 2^20, 0 <= n < 2^31, operands DD_OPERANDS_F16X3 or
+ * DD_OPERANDS_BF16X3; outside them, a NULL buffer the call would touch, no output requested, or a
+ * workspace that is too small or not 16-byte aligned is DD_EINVAL with a message before any
+ * launch.  The workspace (dd_maha_workspace_bytes: host only, 0 for bad arguments, enough for
+ * either call on n rows) holds 4 n bytes of class indices and tiles x segments x 64 KiB of
+ * partials (scatter), or the halves of the rows and of W, 4 (n + D) pad16(D) bytes (dist).
+ * dd_maha_segment_rows is host only too (0 for bad arguments).  No allocation, no
+ * synchronisation inside (graph-capturable); plain vector stores and one 64-bit integer atomic
+ * per non-finite row, no float atomics.
+ * ---------------------------------------------------------------------------------------- */
+size_t dd_maha_workspace_bytes(int64_t n, int32_t D, int32_t operands);
+
+int64_t dd_maha_segment_rows(int64_t n, int32_t D);
+
+int dd_maha_scatter(const float* rows, const int64_t* labels, const int64_t* counts,
+                    const float* mean, int64_t n, int32_t D, int64_t C, int32_t operands,
+                    double* S, int64_t* bad, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
+int dd_maha_dist(const float* rows, const int64_t* labels, const int64_t* counts,
+                 const float* mean, int64_t n, int32_t D, int64_t C, const float* W,
+                 int32_t operands, float* dist, float* accum, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------- *
  * Distance to the nearest neighbour of the same class in feature space: a redundancy signal (a
  * near-duplicate scores close to 0).  Purely additive: dd_abi_version() stays 10.
  *
