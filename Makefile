@@ -26,8 +26,10 @@ all: $(LIB)
 # dd_maha.hip is guarded for the same reason: its centring (a = f - mu, eight independent fp32
 # subtractions per staging step, on which the scatter's exact-equality claim rests) is the shape
 # of loop a compiler packs in pairs.
+# dd_d2.hip too: its products and sums are rounded one by one (__fmul_rn / __fadd_rn), which its
+# bit-for-bit claim against a float32 loop rests on.
 # The older units keep the flags their recorded results and timings were taken with.
-$(OBJDIR)/dd_kmeans.o $(OBJDIR)/dd_kmedoids.o $(OBJDIR)/dd_maha.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+$(OBJDIR)/dd_kmeans.o $(OBJDIR)/dd_kmedoids.o $(OBJDIR)/dd_maha.o $(OBJDIR)/dd_d2.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(OBJDIR)/%.o: data_diet_distributed_amd/csrc/%.hip $(HDR)
 	@mkdir -p $(OBJDIR)

@@ -51,6 +51,7 @@ EXPORTS = (
     "dd_knn_workspace_bytes", "dd_knn",
     "dd_kcenter_workspace_bytes", "dd_kcenter_seed_batch", "dd_kcenter_greedy",
     "dd_kmedoids_workspace_bytes", "dd_kmedoids_greedy",
+    "dd_d2_weights", "dd_d2_propagate", "dd_d2_workspace_bytes", "dd_d2_select",
     "dd_kmeans_workspace_bytes", "dd_kmeans_assign", "dd_kmeans_centroids",
     "dd_maha_workspace_bytes", "dd_maha_segment_rows", "dd_maha_scatter", "dd_maha_dist",
 )
@@ -117,6 +118,10 @@ def lib():
                 "dd_kmedoids_workspace_bytes": (SZ, [I64, I32, I32, P, I64, I32]),
                 "dd_kmedoids_greedy": (I32, [P, P, I64, I32, P, P, I32, P, P, I64, P, I64, I32,
                                              I32, I32, P, P, P, P, P, SZ, P]),
+                "dd_d2_weights": (I32, [P, P, I64, I32, F32, P, P]),
+                "dd_d2_propagate": (I32, [P, P, P, I64, I32, P, P, P]),
+                "dd_d2_workspace_bytes": (SZ, [I64, I32]),
+                "dd_d2_select": (I32, [P, P, P, P, P, I64, I32, I32, I64, P, P, P, P, SZ, P]),
                 "dd_kmeans_workspace_bytes": (SZ, [I64, I32, I32, I32]),
                 "dd_kmeans_assign": (I32, [P, I64, P, I32, I32, I32, I32, P, P, P, P, P, P, P,
                                            SZ, P]),
@@ -863,6 +868,140 @@ def check_kcenter(stat):
     if bad_rows:
         raise ValueError(f"kcenter: {bad_rows} feature row(s) with a NaN or infinite element: the "
                          f"coverage keep-set is undefined")
+
+
+# ---- D2 pruning: message passing on the k-nearest-neighbour graph -------------------------------
+D2_MAX_ROWS = 1 << 21     # DD_D2_MAX_ROWS
+D2_MAX_GROUPS = 16384     # DD_D2_MAX_GROUPS
+
+
+def _d2_graph(what, nbr_id, other, other_name):
+    """nbr_id int64 [n, k] and a matching fp32 [n, k] tensor; returns (n, k)."""
+    _dev(nbr_id, torch.int64, "nbr_id", 2)
+    _dev(other, torch.float32, other_name, 2)
+    n, k = nbr_id.shape
+    if tuple(other.shape) != (n, k):
+        raise ValueError(f"{what}: {other_name} must be [{n}, {k}] like nbr_id (got "
+                         f"{tuple(other.shape)})")
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError(f"{what}: k must be in 1..{KNN_MAX_K} (got {k})")
+    if n > D2_MAX_ROWS:
+        raise ValueError(f"{what}: n = {n} rows is above D2_MAX_ROWS = {D2_MAX_ROWS}")
+    return n, k
+
+
+def d2_weights(dist: torch.Tensor, nbr_id: torch.Tensor, coef: float, w=None) -> torch.Tensor:
+    """w = exp(-coef dist^2) per slot of the graph (dd_d2_weights): dist fp32 [n, k] and nbr_id
+    int64 [n, k] as knn returns them, coef a finite float >= 0.  0 where nbr_id is -1 or dist is
+    not finite; exactly 1 elsewhere at coef = 0.  Returns w fp32 [n, k]."""
+    n, k = _d2_graph("d2_weights", nbr_id, dist, "dist")
+    coef = float(coef)
+    if not (0.0 <= coef < float("inf")):
+        raise ValueError(f"d2_weights: coef must be finite and >= 0 (got {coef!r})")
+    if w is None:
+        w = torch.empty_like(dist)
+    _same_shape("w", w, (n, k))
+    if n:
+        rc = lib().dd_d2_weights(_dev(dist, torch.float32, "dist"),
+                                 _dev(nbr_id, torch.int64, "nbr_id"), n, k, coef,
+                                 _dev(w, torch.float32, "w"), _stream(dist))
+        _check(rc, "dd_d2_weights")
+    return w
+
+
+def d2_propagate(x0: torch.Tensor, nbr_id: torch.Tensor, w: torch.Tensor, *, check: bool = True):
+    """One round of forward message passing (dd_d2_propagate): x1[i] = x0[i] + sum_j w[i, j]
+    x0[nbr_id[i, j]] over the used slots in ascending order, every product and sum rounded to
+    fp32 on its own.  Returns (x1 fp32 [n], bad int32 [1]): bad counts the rows whose x0 or x1 is
+    not finite; with check it is read back (one sync) and raises ValueError."""
+    n, k = _d2_graph("d2_propagate", nbr_id, w, "w")
+    _dev(x0, torch.float32, "x0", 1)
+    if x0.numel() != n:
+        raise ValueError(f"d2_propagate: x0 must have {n} elements (got {x0.numel()})")
+    x1 = torch.empty_like(x0)
+    bad = torch.zeros(1, dtype=torch.int32, device=x0.device)
+    if n:
+        rc = lib().dd_d2_propagate(_dev(x0, torch.float32, "x0"),
+                                   _dev(nbr_id, torch.int64, "nbr_id"),
+                                   _dev(w, torch.float32, "w"), n, k,
+                                   _dev(x1, torch.float32, "x1"),
+                                   ctypes.c_void_p(bad.data_ptr()), _stream(x0))
+        _check(rc, "dd_d2_propagate")
+    if check:
+        check_d2(bad.tolist() + [0])
+    return x1, bad
+
+
+def d2_workspace_bytes(n: int, G: int = 1) -> int:
+    """Bytes of d2_select's workspace (dd_d2_workspace_bytes; 0 for sizes outside the entry
+    point's limits)."""
+    return int(lib().dd_d2_workspace_bytes(int(n), int(G)))
+
+
+def d2_select(x: torch.Tensor, nbr_id: torch.Tensor, w: torch.Tensor, quota, groups=None, *,
+              check: bool = True):
+    """The sequential D2 selection (dd_d2_select), one persistent workgroup: until sum(quota) rows
+    are picked, take the live row with the largest x (a tie to the smaller index), retire it, and
+    unless its group's quota is exhausted record it and lower each live neighbour v = nbr_id[s, j]
+    by w[s, j] * x[s].  x fp32 [n] (not modified), nbr_id int64 [n, k] (row indices, -1: unused),
+    w fp32 [n, k], quota: host ints [G], groups int64 [n] in [0, G) (None: one group).
+
+    Returns (picked int64 [total], value fp32 [total], bad int32 [1]), total = sum(quota): the
+    rows in pick order and their score when picked, -1 in the unfilled tail; bad counts the
+    non-finite scores and the groups outside [0, G).  With check it is read back (one sync) and
+    raises ValueError; check=False leaves it to the caller."""
+    what = "d2_select"
+    n, k = _d2_graph(what, nbr_id, w, "w")
+    _dev(x, torch.float32, "x", 1)
+    if x.numel() != n:
+        raise ValueError(f"{what}: x must have {n} elements (got {x.numel()})")
+    quota = [int(q) for q in quota]
+    G = len(quota)
+    if not 1 <= G <= D2_MAX_GROUPS:
+        raise ValueError(f"{what}: need 1 <= G <= {D2_MAX_GROUPS} groups (got {G})")
+    total = sum(quota)
+    if any(q < 0 for q in quota) or total > n:
+        raise ValueError(f"{what}: negative quota, or quotas above the {n} rows")
+    if groups is None and G != 1:
+        raise ValueError(f"{what}: G > 1 needs `groups`")
+    if groups is not None:
+        _dev(groups, torch.int64, "groups", 1)
+        if groups.numel() != n:
+            raise ValueError(f"{what}: groups must have one entry per row")
+    dev = x.device
+    picked = torch.full((total,), -1, dtype=torch.int64, device=dev)
+    value = torch.full((total,), -1.0, dtype=torch.float32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n:
+        need = int(lib().dd_d2_workspace_bytes(n, G))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        quota_d = torch.tensor(quota, dtype=torch.int64).to(dev)
+        e0 = _t0(x, always=True)
+        rc = lib().dd_d2_select(
+            _dev(x, torch.float32, "x"), _dev(nbr_id, torch.int64, "nbr_id"),
+            _dev(w, torch.float32, "w"), _opt(groups, torch.int64, "groups"),
+            _dev(quota_d, torch.int64, "quota"), n, k, G, total,
+            _opt(picked if total else None, torch.int64, "picked"),
+            _opt(value if total else None, torch.float32, "value"),
+            ctypes.c_void_p(bad.data_ptr()), _dev(ws, torch.uint8, "workspace"), need,
+            _stream(x))
+        _check(rc, "dd_d2_select")
+        # per pick: a block scanned, the row's slots read, k scores updated, k + 1 blocks re-read
+        _t1(e0, "select", 4.0 * n + total * (1024.0 * (k + 2) + 20.0 * k), x)
+    if check:
+        check_d2([0] + bad.tolist())
+    return picked, value, bad
+
+
+def check_d2(stat):
+    """Raise ValueError on the D2 counts (host ints): d2_propagate's non-finite scores, then
+    d2_select's non-finite scores and groups out of range."""
+    bad_keys, bad_sel = (int(v) for v in stat)
+    if bad_keys:
+        raise ValueError(f"d2: {bad_keys} NaN or infinite score(s): the keep-set is undefined")
+    if bad_sel:
+        raise ValueError(f"d2: {bad_sel} non-finite propagated score(s) or group(s) out of "
+                         f"range: the keep-set is undefined")
 
 
 # ---- distance to the nearest k-means centroid ---------------------------------------------------

@@ -34,7 +34,12 @@ DEFAULTS = {
     "select_fill": "score",           # score (the rank cut) | kcenter (coverage: greedy k-center)
     "kcenter_seed_frac": 0.0,         # share of a quota seeded by the score (at least one seed)
     "kcenter_objective": "radius",    # radius (farthest-first) | inertia (greedy k-medoids)
-    "kcenter_ckpt": -1,               # the checkpoint whose feature rows span the space
+    "kcenter_ckpt": -1,               # the checkpoint whose feature rows the row-based
+    #                                   selections read (the kcenter fill, the d2 diversity)
+    "select_diversity": "none",       # none | d2 (D2 pruning: message passing on the kNN graph)
+    "d2_k": 10,                       # neighbours per example of the d2 graph (1..16)
+    "d2_gamma_f": 1.0,                # sharpness of the forward edge weights (>= 0)
+    "d2_gamma_r": 1.0,                # sharpness of the reverse edge weights (>= 0)
     "score_checkpoints": 1,           # K (seed{k}/ckpt_{epoch}.pth when K > 1)
     "score_epoch": 19,
     "bn_mode": "batch",               # EL2N BN: batch (reference) | running (eval)

@@ -525,8 +525,9 @@ class ForwardScores:
     def __init__(self, cfg, labels: torch.Tensor, linear, group=None,
                  counter: Optional[torch.Tensor] = None, kcenter_ckpt: Optional[int] = None):
         n, methods = labels.numel(), cfg.methods
-        # the kcenter fill (ScoreConfig.select_fill): every rank's feature rows of checkpoint
-        # `kcenter_ckpt` (0-based) are kept for run()'s selection
+        # the row-based selections (ScoreConfig.select_fill "kcenter", select_diversity "d2"):
+        # every rank's feature rows of checkpoint `kcenter_ckpt` (0-based) are kept for run()'s
+        # selection
         self.kcenter_ckpt, self.kcenter_rows, self._ckpts_done = kcenter_ckpt, None, 0
         logit = [m for m in methods if m in LOGIT_FAMILY]
         self.logit = LogitScores(logit, n, labels.device) if logit else None
@@ -554,7 +555,7 @@ class ForwardScores:
         self.features = None
         by_features = self.proto or self.nn or self.knn or self.kmeans or self.maha
         if kcenter_ckpt is not None:
-            _check_width("kcenter", linear.in_features)
+            _check_width("d2" if cfg.select_diversity == "d2" else "kcenter", linear.in_features)
         if by_features or kcenter_ckpt is not None:
             self.features = torch.empty((n, linear.in_features), dtype=torch.float32,
                                         device=labels.device)

@@ -433,7 +433,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                   *, dataset=None, subset_index_path=None, return_indices=False,
                   fast: bool = True, refine="auto", policy="global", skip=0, score="el2n",
                   knn_k=5, fill="score", seed_frac=0.0, kmeans_k=0, kmeans_iters=20,
-                  objective="radius", maha_shrink=0.01):
+                  objective="radius", maha_shrink=0.01, diversity="none", d2_k=10,
+                  d2_gamma_f=1.0, d2_gamma_r=1.0):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
@@ -473,10 +474,16 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     distances to the nearest kept example the most (greedy k-medoids, dd_kmedoids_greedy; a
     group of at most _capi.KMEDOIDS_MAX_GROUP_ROWS examples, so large sets need a class policy),
     and the record also holds each group's inertia.
+    diversity / d2_k / d2_gamma_f / d2_gamma_r (ScoreConfig.select_diversity and its fields; the
+    three numbers are checked whatever the diversity): "d2" is D2 pruning on the d2_k-nearest-
+    neighbour graph of the visited examples' feature rows: a score absorbs its neighbours' (edge
+    weights exp(-d2_gamma_f d^2 / mean d^2)), then the quotas are filled greedily by the updated
+    score, every pick lowering its neighbours' (d2_gamma_r; dd_d2_select).  It needs fill="score"
+    and skip = 0 and is never refined; the record holds the graph's scale.
     "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
     over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
     score="el2n"."""
-    from .methods import check_objective, check_selection, check_shrink
+    from .methods import check_diversity, check_objective, check_selection, check_shrink
     from .scoring import normalize_refine, select_with_policy
     refine = normalize_refine(refine)
     if score in ("variability", "grand", "proto"):
@@ -501,11 +508,15 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     skip = check_selection(policy, skip, "policy", "skip", fill=fill, seed_frac=seed_frac,
                            fill_name="fill", frac_name="seed_frac")
     check_objective(objective, "objective")
-    kcenter = fill == "kcenter"
+    d2_k, d2_gamma_f, d2_gamma_r = check_diversity(
+        diversity, d2_k, d2_gamma_f, d2_gamma_r, fill, skip, name="diversity", fill_name="fill",
+        skip_name="skip")
+    d2 = diversity == "d2"
+    kcenter = fill == "kcenter" or d2  # (the selections that read the visited rows)
     default_rule = policy == "global" and skip == 0 and not kcenter
     if refine is True and not default_rule:
         raise ValueError("refine=True needs the default selection (policy='global', skip=0, "
-                         "fill='score')")
+                         "fill='score', diversity='none')")
     if torch.device(device).type != "cuda":
         raise ValueError("sparse_loader runs its kernels on a GPU device (libdd.so)")
     module = net.module if hasattr(net, "module") else net
@@ -541,7 +552,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
             labels_visit, ncls = seen["labels"], seen["num_classes"] or 1
         pos, sparse_loader.last_selection = select_with_policy(
             scores.contiguous(), labels_visit, ncls, samples, policy, int(skip), fill=fill,
-            seed_frac=seed_frac, rows=seen["rows"] if kcenter else None, objective=objective)
+            seed_frac=seed_frac, rows=seen["rows"] if kcenter else None, objective=objective,
+            diversity=diversity, d2_k=d2_k, gamma_f=d2_gamma_f, gamma_r=d2_gamma_r)
         kept = visit[pos]
     elif fp is not None and refine is True and 0 < samples < scores.numel():
         pos, sparse_loader.last_refine = refine_fast_keep_set(
@@ -574,12 +586,16 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                                 "select_policy": policy, "select_skip": int(skip),
                                 "class_quota": sparse_loader.last_selection["class_quota"],
                                 "class_skip": sparse_loader.last_selection["class_skip"]}),
-                            **({} if not kcenter else {
+                            **({} if not d2 else {
+                                "select_diversity": diversity, "d2_k": d2_k,
+                                "d2_gamma_f": d2_gamma_f, "d2_gamma_r": d2_gamma_r,
+                                "d2_scale": sparse_loader.last_selection["d2_scale"]}),
+                            **({} if fill != "kcenter" else {
                                 "select_fill": fill, "kcenter_seed_frac": float(seed_frac),
                                 "class_seeds": sparse_loader.last_selection["class_seeds"],
                                 "radius": json_radius(
                                     sparse_loader.last_selection["radius"])}),
-                            **({} if not kcenter or objective == "radius" else {
+                            **({} if fill != "kcenter" or objective == "radius" else {
                                 "kcenter_objective": objective,
                                 "inertia": json_radius(
                                     sparse_loader.last_selection["inertia"])})})

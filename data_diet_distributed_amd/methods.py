@@ -139,6 +139,45 @@ def check_objective(objective, name="kcenter_objective") -> str:
     return objective
 
 
+# Whether the rank cut (select_fill "score") also weighs coverage:
+#   "none"  the rank cut as it is
+#   "d2"    D2 pruning (Maharana, Yadav & Bansal): the examples sit on the d2_k-nearest-neighbour
+#           graph of their feature rows (dd_knn, all classes), edge weights exp(-gamma d^2 / s)
+#           with s the mean finite squared neighbour distance.  One round of forward message
+#           passing lets a score absorb its neighbours' (weights by d2_gamma_f, dd_d2_propagate);
+#           then the groups' quotas are filled greedily by the updated score, every pick lowering
+#           its live neighbours' scores by weight x its own (weights by d2_gamma_r, dd_d2_select),
+#           so the next pick moves elsewhere.  Both gammas large: every weight is 0 and the
+#           keep-set is the rank cut's.
+SELECT_DIVERSITY = ("none", "d2")
+
+
+def check_diversity(diversity, k=10, gamma_f=1.0, gamma_r=1.0, fill="score", skip=0, *,
+                    name="select_diversity", k_name="d2_k", gamma_f_name="d2_gamma_f",
+                    gamma_r_name="d2_gamma_r", fill_name="select_fill",
+                    skip_name="select_skip"):
+    """ScoreConfig's select_diversity / d2_k / d2_gamma_f / d2_gamma_r, and select_with_policy's /
+    sparse_loader's under their own names: a known diversity, 1 <= k <= _capi.KNN_MAX_K, finite
+    gammas >= 0 (all checked whatever the diversity), and "d2" with the score fill and no skip.
+    Returns (k, gamma_f, gamma_r) as an int and two floats."""
+    if diversity not in SELECT_DIVERSITY:
+        raise ValueError(f"{name} must be one of {SELECT_DIVERSITY} (got {diversity!r})")
+    if (isinstance(k, bool) or not isinstance(k, (int, np.integer))
+            or not 1 <= k <= _capi.KNN_MAX_K):
+        raise ValueError(f"{k_name} must be an integer in 1..{_capi.KNN_MAX_K} (got {k!r})")
+    for g_name, g in ((gamma_f_name, gamma_f), (gamma_r_name, gamma_r)):
+        if (isinstance(g, bool) or not isinstance(g, (int, float, np.integer, np.floating))
+                or not 0.0 <= float(g) < float("inf")):
+            raise ValueError(f"{g_name} must be a finite number >= 0 (got {g!r})")
+    if diversity == "d2" and fill != "score":
+        raise ValueError(f"{name}='d2' needs {fill_name}='score' (got {fill!r}): the kcenter "
+                         f"fill is a coverage rule of its own")
+    if diversity == "d2" and skip:
+        raise ValueError(f"{name}='d2' needs {skip_name}=0 (got {skip!r}): an offset window is "
+                         f"a rank cut's notion")
+    return int(k), float(gamma_f), float(gamma_r)
+
+
 def seed_counts(quotas, seed_frac: float):
     """Seeds per group of the kcenter fill: max(1, floor(seed_frac * q)) for a quota q > 0, none
     for q = 0 (never more than q: seed_frac <= 1)."""

@@ -24,6 +24,9 @@ rest (config.DEFAULTS):
                      of a quota seeded by the score; kcenter_ckpt: whose rows (default: the last);
                      kcenter_objective: radius (farthest-first) | inertia (greedy k-medoids,
                      --fill-objective)
+  select_diversity   none | d2: D2 pruning on the d2_k-nearest-neighbour graph of kcenter_ckpt's
+                     feature rows (--diversity, --d2-k); d2_gamma_f / d2_gamma_r: the forward /
+                     reverse edge weights' sharpness (--d2-gamma-f, --d2-gamma-r)
   bn_mode            EL2N BatchNorm: batch|train (reference) or running|eval
   pegrad_method      auto | direct | ghost             grand_batch   GraNd chunk
   score_gpus         ranks (one per GPU; self-launched here, or run under torchrun)
@@ -150,6 +153,9 @@ def engine_config(cfg):
                        kcenter_seed_frac=float(cfg.get("kcenter_seed_frac", 0.0)),
                        kcenter_ckpt=int(cfg.get("kcenter_ckpt", -1)),
                        kcenter_objective=cfg.get("kcenter_objective", "radius"),
+                       select_diversity=cfg.get("select_diversity", "none"),
+                       d2_k=cfg.get("d2_k", 10), d2_gamma_f=cfg.get("d2_gamma_f", 1.0),
+                       d2_gamma_r=cfg.get("d2_gamma_r", 1.0),
                        **SCORE_PRECISIONS[prec])
 
 
@@ -215,6 +221,11 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
             if sel.get("objective", "radius") != "radius":  # (the default: metadata unchanged)
                 meta.update(kcenter_objective=sel["objective"],
                             inertia=json_radius(sel["inertia"]))
+        if sel.get("diversity") == "d2":  # (a run without it: metadata unchanged)
+            meta.update(select_diversity=sel["diversity"], d2_k=sel["d2_k"],
+                        d2_gamma_f=sel["d2_gamma_f"], d2_gamma_r=sel["d2_gamma_r"],
+                        d2_scale=sel["d2_scale"], kcenter_ckpt=ecfg.kcenter_ckpt % K,
+                        select_policy=sel["policy"], class_quota=sel["class_quota"])
         out_path = out_path or cfg.get("subset_index_path")
         if out_path:
             path = write_subset_index(out_path, kept_np, meta)
@@ -244,20 +255,33 @@ def parse(argv=None):
     ap.add_argument("--fill-objective", default=None, choices=("radius", "inertia"),
                     help="what the kcenter fill minimises (default: kcenter_objective of the "
                          "config)")
+    ap.add_argument("--diversity", default=None, choices=("none", "d2"),
+                    help="whether the score fill weighs coverage (default: select_diversity of "
+                         "the config)")
+    ap.add_argument("--d2-k", type=int, default=None,
+                    help="neighbours per example of the d2 graph (default: d2_k of the config)")
+    ap.add_argument("--d2-gamma-f", type=float, default=None,
+                    help="sharpness of the forward edge weights (default: d2_gamma_f)")
+    ap.add_argument("--d2-gamma-r", type=float, default=None,
+                    help="sharpness of the reverse edge weights (default: d2_gamma_r)")
     return ap.parse_args(argv)
+
+
+def apply_overrides(cfg: dict, args) -> dict:
+    """The command line's selection options written over the config's keys (in place)."""
+    for key, v in (("select_policy", args.policy), ("select_skip", args.skip),
+                   ("select_fill", args.fill), ("kcenter_objective", args.fill_objective),
+                   ("select_diversity", args.diversity), ("d2_k", args.d2_k),
+                   ("d2_gamma_f", args.d2_gamma_f), ("d2_gamma_r", args.d2_gamma_r)):
+        if v is not None:
+            cfg[key] = v
+    return cfg
 
 
 def main(argv=None):
     args = parse(argv)
     cfg = config_mod.load_config(args.config)
-    if args.policy is not None:
-        cfg["select_policy"] = args.policy
-    if args.skip is not None:
-        cfg["select_skip"] = args.skip
-    if args.fill is not None:
-        cfg["select_fill"] = args.fill
-    if args.fill_objective is not None:
-        cfg["kcenter_objective"] = args.fill_objective
+    apply_overrides(cfg, args)
     gpus = args.gpus or int(cfg.get("score_gpus", 1))
     if gpus > 1 and not launch.under_launcher():
         rest = list(sys.argv[1:] if argv is None else argv)

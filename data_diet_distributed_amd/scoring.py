@@ -50,8 +50,9 @@ from .forward_scores import (ForwardScores, check_class_sizes,  # noqa: F401
                              check_no_singleton_class, ensemble_mean, nearest_same_class)
 from .methods import (CLUSTER_METHODS, COVARIANCE_METHODS, FEATURE_METHODS,  # noqa: F401
                       FORWARD_FAMILY, FORWARD_SCORES, KNN_METHODS, LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS,
-                      SELECT_FILLS, SELECT_POLICIES, check_fill, check_objective,
-                      check_selection, check_shrink, known, pass_of, refinable, seed_counts)
+                      SELECT_DIVERSITY, SELECT_FILLS, SELECT_POLICIES, check_diversity, check_fill,
+                      check_objective, check_selection, check_shrink, known, pass_of, refinable,
+                      seed_counts)
 from .resnet import ResNet
 
 MEAN = (0.4914, 0.4822, 0.4465)  # reference data/loader.py:10
@@ -153,7 +154,8 @@ class ScoreConfig:
     # "kcenter" is coverage: group g (the whole set under "global", a class otherwise) seeds with
     # its top max(1, floor(kcenter_seed_frac * q_g)) examples by select_by, and farthest-first
     # traversal of checkpoint kcenter_ckpt's pooled feature rows (an index in [-K, K); the last
-    # by default) picks the other q_g - m_g (select_with_policy; dd_kcenter_greedy).  It needs
+    # by default: the checkpoint whose feature rows the row-based selections read) picks the
+    # other q_g - m_g (select_with_policy; dd_kcenter_greedy).  It needs
     # select_skip = 0, is never refined (refine=True is rejected, "auto" behaves as False), and
     # last_selection records the seeds and each group's covering radius.
     # kcenter_objective (methods.KCENTER_OBJECTIVES) is what the picks minimise: "radius" is the
@@ -166,6 +168,17 @@ class ScoreConfig:
     kcenter_seed_frac: float = 0.0
     kcenter_ckpt: int = -1
     kcenter_objective: str = "radius"
+    # Whether the score fill also weighs coverage (methods.SELECT_DIVERSITY): "d2" is D2 pruning:
+    # on the d2_k-nearest-neighbour graph of checkpoint kcenter_ckpt's feature rows a score first
+    # absorbs its neighbours' (edge weights exp(-d2_gamma_f d^2 / mean d^2)), then the quotas of
+    # the policy are filled greedily by the updated score, every pick lowering its neighbours'
+    # scores (weights by d2_gamma_r; select_with_policy, dd_d2_select).  It needs select_fill =
+    # "score" and select_skip = 0 and is never refined (refine=True is rejected, "auto" behaves as
+    # False).  d2_k and the gammas are validated whatever the diversity, like kcenter_seed_frac.
+    select_diversity: str = "none"
+    d2_k: int = 10
+    d2_gamma_f: float = 1.0
+    d2_gamma_r: float = 1.0
 
     def __post_init__(self):
         self.methods = tuple(self.methods)
@@ -215,10 +228,13 @@ class ScoreConfig:
                                                                  (int, np.integer)):
             raise ValueError(f"kcenter_ckpt must be an integer (got {self.kcenter_ckpt!r})")
         self.kcenter_ckpt = int(self.kcenter_ckpt)
+        self.d2_k, self.d2_gamma_f, self.d2_gamma_r = check_diversity(
+            self.select_diversity, self.d2_k, self.d2_gamma_f, self.d2_gamma_r,
+            self.select_fill, self.select_skip)
         if self.refine is True and not self.default_selection():
             raise ValueError("refine=True needs the default selection (select_policy='global', "
-                             "select_skip=0, select_fill='score'): the refinement re-scores "
-                             "around one threshold")
+                             "select_skip=0, select_fill='score', select_diversity='none'): the "
+                             "refinement re-scores around one threshold")
         if self.refine is True and not refinable(self.select_by):
             raise ValueError(f"refine=True re-scores EL2N or GraNd only (select_by="
                              f"{self.select_by!r})")
@@ -228,7 +244,14 @@ class ScoreConfig:
 
     def default_selection(self) -> bool:
         return (self.select_policy == "global" and self.select_skip == 0
-                and self.select_fill == "score")
+                and self.select_fill == "score" and self.select_diversity == "none")
+
+    def row_selection(self) -> Optional[str]:
+        """The selection that reads checkpoint kcenter_ckpt's feature rows, by the name of its
+        field's value ("kcenter" or "d2"), or None."""
+        if self.select_fill == "kcenter":
+            return "select_fill='kcenter'"
+        return "select_diversity='d2'" if self.select_diversity == "d2" else None
 
 
 def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
@@ -277,7 +300,8 @@ def apportion(total: int, caps, rule: str = "stratified") -> List[int]:
 def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: str = "global",
                        skip: int = 0, check_nan: bool = True, fill: str = "score",
                        seed_frac: float = 0.0, rows: Optional[torch.Tensor] = None,
-                       objective: str = "radius"):
+                       objective: str = "radius", diversity: str = "none", d2_k: int = 10,
+                       gamma_f: float = 1.0, gamma_r: float = 1.0):
     """The keep-set of `k` of the n = keys.numel() examples under a selection policy
     (ScoreConfig.select_policy / select_skip), in dd_select_topk's order: key descending, ties
     by ascending index.  `labels` (int64 [n], on the keys' device) and `num_classes` are read
@@ -306,7 +330,17 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     and "radius" are as above, and the record also gets "objective" and "inertia": per group that
     sum over its unkept rows at the end (+inf for a non-empty group that keeps nothing), from
     the same one read.  A group holds at most _capi.KMEDOIDS_MAX_GROUP_ROWS rows, so "global"
-    serves small sets only: a larger one raises and names the class policies."""
+    serves small sets only: a larger one raises and names the class policies.
+
+    diversity="d2" (ScoreConfig.select_diversity; needs fill = "score", skip = 0 and `rows`): D2
+    pruning.  The groups and quotas are the policy's ("global": one group with quota k).  dd_knn
+    gives every row its d2_k nearest other rows of `rows` (nbr_id, dist); scale = the float64 mean
+    of the finite squared distances (one read: the host makes coef = gamma / scale, a float, from
+    it; gamma = 0 gives weights of 1); dd_d2_weights makes the forward (gamma_f) and reverse
+    (gamma_r) weights, dd_d2_propagate lets every key absorb its neighbours' and dd_d2_select
+    fills the quotas.  kept = the picks in pick order.  The record gains {"diversity", "d2_k",
+    "d2_gamma_f", "d2_gamma_r", "d2_scale"}.  One read after the kernels covers the non-finite
+    keys and dd_d2_select's count; either raises ValueError."""
     if policy not in SELECT_POLICIES:
         raise ValueError(f"select policy must be one of {SELECT_POLICIES} (got {policy!r})")
     n, k, skip = keys.numel(), int(k), int(skip)
@@ -316,8 +350,20 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     seed_frac = check_fill(fill, seed_frac, skip, fill_name="fill", frac_name="seed_frac",
                            skip_name="skip")
     check_objective(objective, "objective")
+    d2_k, gamma_f, gamma_r = check_diversity(
+        diversity, d2_k, gamma_f, gamma_r, fill, skip, name="diversity", k_name="d2_k",
+        gamma_f_name="gamma_f", gamma_r_name="gamma_r", fill_name="fill", skip_name="skip")
     rec = {"policy": policy, "skip": skip, "class_counts": None, "class_skip": None,
            "class_quota": None}
+    d2 = diversity == "d2"
+    if d2:
+        rec.update(diversity=diversity, d2_k=d2_k, d2_gamma_f=gamma_f, d2_gamma_r=gamma_r,
+                   d2_scale=None)
+        if rows is None or rows.dim() != 2 or rows.shape[0] != n:
+            raise ValueError(f"diversity='d2' needs rows [n = {n}, D] (got "
+                             f"{None if rows is None else tuple(rows.shape)})")
+        if n > _capi.D2_MAX_ROWS:
+            raise ValueError(f"diversity='d2' holds at most {_capi.D2_MAX_ROWS} rows (n = {n})")
     if fill == "kcenter":
         rec.update(fill=fill, class_seeds=None, radius=None)
         if objective != "radius":
@@ -334,6 +380,9 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
                                  f"('stratified' or 'balanced'), whose groups are the classes")
             return _kcenter_fill(keys, None, [n], [k], rows.contiguous(), seed_frac, rec,
                                  check_nan, objective)
+        if d2:
+            return _d2_fill(keys, None, [k], rows.contiguous(), d2_k, gamma_f, gamma_r, rec,
+                            check_nan)
         kept = _capi.select_topk(keys, skip + k, check_nan=check_nan)[0]
         return (kept[skip:] if skip else kept), rec
     C = int(num_classes)
@@ -349,7 +398,48 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     if fill == "kcenter":
         return _kcenter_fill(keys, labels, n_c, q, rows.contiguous(), seed_frac, rec, check_nan,
                              objective)
+    if d2:
+        if C > _capi.D2_MAX_GROUPS:
+            raise ValueError(f"diversity='d2' holds at most {_capi.D2_MAX_GROUPS} groups "
+                             f"(num_classes = {C})")
+        return _d2_fill(keys, labels, q, rows.contiguous(), d2_k, gamma_f, gamma_r, rec,
+                        check_nan)
     kept = _capi.select_topk_by_class(keys, labels, C, s, q, k_total=k, check=check_nan)[0]
+    return kept, rec
+
+
+def _d2_fill(keys, labels, quotas, rows, d2_k, gamma_f, gamma_r, rec, check_nan):
+    """select_with_policy's D2 selection over the groups `labels` (None: one group) with
+    `quotas`; completes and returns (kept, rec)."""
+    n, dev = keys.numel(), keys.device
+    if n == 0:
+        return torch.empty(0, dtype=torch.int64, device=dev), rec
+    ids = torch.arange(n, dtype=torch.int64, device=dev)
+    dist = torch.empty((n, d2_k), dtype=torch.float32, device=dev)
+    nbr = torch.empty((n, d2_k), dtype=torch.int64, device=dev)
+    _capi.knn(rows, ids, rows, ids, d2_k, dist=dist, nbr_id=nbr)
+    # the scale: the float64 mean of the finite squared neighbour distances (the one read the
+    # host needs before the weights: coef is its float)
+    fin = torch.isfinite(dist)
+    sq = torch.where(fin, dist.to(torch.float64) ** 2, torch.zeros((), dtype=torch.float64,
+                                                                   device=dev))
+    total, cnt = torch.stack([sq.sum(), fin.sum().to(torch.float64)]).tolist()
+    scale = total / cnt if cnt else 0.0
+    if (gamma_f or gamma_r) and not 0.0 < scale < float("inf"):
+        raise ValueError(f"diversity='d2': the mean squared neighbour distance is {scale!r} "
+                         f"(every row a duplicate, or no finite neighbour): no edge weight is "
+                         f"defined")
+    coef = [float(np.float32(g / scale)) if g else 0.0 for g in (gamma_f, gamma_r)]
+    if not all(c < float("inf") for c in coef):
+        raise ValueError(f"diversity='d2': gamma / scale = {max(coef)!r} is not a finite float "
+                         f"(gamma_f={gamma_f!r}, gamma_r={gamma_r!r}, scale={scale!r})")
+    w_f = _capi.d2_weights(dist, nbr, coef[0])
+    w_r = w_f if coef[1] == coef[0] else _capi.d2_weights(dist, nbr, coef[1])
+    x1, bad_keys = _capi.d2_propagate(keys.contiguous(), nbr, w_f, check=False)
+    kept, _, bad_sel = _capi.d2_select(x1, nbr, w_r, quotas, labels, check=False)
+    host = torch.cat([bad_keys, bad_sel]).tolist()  # the one read after the kernels
+    _capi.check_d2([host[0] if check_nan else 0, host[1]])
+    rec.update(d2_scale=scale)
     return kept, rec
 
 
@@ -591,12 +681,12 @@ class ScoringEngine:
     def __init__(self, models: List[ResNet], cfg: ScoreConfig, device):
         if not models:
             raise ValueError("need at least one checkpoint model")
-        if cfg.select_fill == "kcenter":
+        if cfg.row_selection() is not None:
             if not -len(models) <= cfg.kcenter_ckpt < len(models):
                 raise ValueError(f"kcenter_ckpt={cfg.kcenter_ckpt} outside [-{len(models)}, "
                                  f"{len(models)}): {len(models)} checkpoint(s)")
             if "el2n" not in map(pass_of, cfg.methods):
-                raise ValueError("select_fill='kcenter' takes its feature rows from the EL2N "
+                raise ValueError(f"{cfg.row_selection()} takes its feature rows from the EL2N "
                                  "forward: request at least one score of that forward "
                                  f"(methods={cfg.methods})")
         self.models = models
@@ -630,7 +720,8 @@ class ScoringEngine:
         self._wss: Dict[int, torch.Tensor] = {}  # pegrad workspace per lane
         self.last_refine: Optional[dict] = None  # what the last run()'s _refine did
         # the last run()'s selection: {"policy", "skip", "class_counts", "class_skip",
-        # "class_quota"}, with the kcenter fill also {"fill", "class_seeds", "radius"}
+        # "class_quota"}, with the kcenter fill also {"fill", "class_seeds", "radius"}, with the
+        # d2 diversity {"diversity", "d2_k", "d2_gamma_f", "d2_gamma_r", "d2_scale"}
         # (select_with_policy's record)
         self.last_selection: Optional[dict] = None
         # set when a GraNd forward on fp16 operand halves overflowed and the engine re-scored
@@ -638,8 +729,8 @@ class ScoringEngine:
         self.grand_fallback: Optional[str] = None
         self.fallback: Dict[str, str] = {}  # method -> why it was re-scored on bf16 halves
         self._bad = None  # the last score_shard's count of labels outside [0, C)
-        # the kcenter fill's feature rows of the whole dataset (checkpoint kcenter_ckpt's, from
-        # the last score_shard)
+        # the row-based selections' (the kcenter fill's, the d2 diversity's) feature rows of the
+        # whole dataset (checkpoint kcenter_ckpt's, from the last score_shard)
         self._kcenter_rows: Optional[torch.Tensor] = None
         # optional heartbeat, called with a short message every `progress_every` launch chunks
         # (a long config-5 pass otherwise prints nothing for minutes)
@@ -881,7 +972,7 @@ class ScoringEngine:
                             counter=self._bad if kinds[0] == "el2n" else None,
                             # (no EL2N pass: _validate's re-scoring of GraNd alone, which
                             # leaves the rows of the first scoring in place)
-                            kcenter_ckpt=(cfg.kcenter_ckpt % K if cfg.select_fill == "kcenter"
+                            kcenter_ckpt=(cfg.kcenter_ckpt % K if cfg.row_selection() is not None
                                           and "el2n" in kinds else None))
         grand = (torch.zeros(n, dtype=torch.float32, device=self.device)
                  if "grand" in kinds else None)
@@ -1047,8 +1138,9 @@ class ScoringEngine:
             kept, self.last_selection = select_with_policy(
                 keys, all_labels, self.models[0].linear.out_features, k, c.select_policy,
                 c.select_skip, check_nan, fill=c.select_fill, seed_frac=c.kcenter_seed_frac,
-                objective=c.kcenter_objective,
-                rows=self._kcenter_rows if c.select_fill == "kcenter" else None)
+                objective=c.kcenter_objective, diversity=c.select_diversity, d2_k=c.d2_k,
+                gamma_f=c.d2_gamma_f, gamma_r=c.d2_gamma_r,
+                rows=self._kcenter_rows if c.row_selection() is not None else None)
             return kept
 
         full, kept, k = sharded_job(score, N, B, sparsity, self.cfg.select_by, select,

@@ -964,6 +964,82 @@ int dd_kmedoids_greedy(const float* rows, const int64_t* ids, int64_t n, int32_t
                        size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------- *
+ * D2 pruning (Maharana, Yadav & Bansal, "D2 Pruning: Message Passing for Balancing Diversity and
+ * Difficulty in Data Pruning") on a k-nearest-neighbour graph: the keep-set that weighs difficulty
+ * against coverage.  Purely additive: dd_abi_version() stays 10.
+ *
+ * The graph is dd_knn's: nbr_id int64 [n][k], row i's neighbours as ROW INDICES in [0, n) or -1
+ * for an unused slot (an index outside [-1, n) is skipped like -1), and dist fp32 [n][k].
+ *
+ * dd_d2_weights: w[e] = expf(-((coef * dist[e]) * dist[e])) for e < n k, the two products rounded
+ *   to fp32 one after the other and the exponential the accurate expf (<= 1 ulp), not the fast
+ *   intrinsic.  coef >= 0 and finite (host).  A slot with nbr_id == -1 or a NaN or infinite dist
+ *   gets w = 0; coef == 0 gives exactly 1 on every other slot.
+ *
+ * dd_d2_propagate: forward message passing, one round.
+ *   x1[i] = x0[i] + sum over slots j = 0 .. k - 1 in ascending order, skipping nbr_id[i][j] == -1,
+ *           of w[i][j] * x0[nbr_id[i][j]]
+ *   reading the ORIGINAL x0 throughout (x1 must not be x0).  Every product and every sum is a
+ *   separately rounded fp32 operation, never contracted to an fma: a float32 loop in the same order
+ *   reproduces it bit for bit.  bad[0] += the rows whose x0 or x1 is NaN or infinite (the caller
+ *   clears it).
+ *
+ * dd_d2_select: the sequential selection.  x fp32 [n] (read; the working copy lives in the
+ *   workspace), w fp32 [n][k] the reverse weights, group int64 [n] (NULL: one group, G == 1), quota
+ *   int64 [G] on the device, total = sum(quota) on the host (the loop bound and the length of the
+ *   outputs; a quota below 0 counts as 0).
+ *   Repeat until `total` rows are picked or no live row is left:
+ *     take the live row s with the largest x, a tie going to the smaller index, and retire it;
+ *     if quota[group[s]] is exhausted, s is dropped: neither recorded nor sending a message;
+ *     otherwise picked[t] = s, value[t] = x[s] as it is at that moment, the quota is decremented,
+ *     and for each slot j in ascending order with v = nbr_id[s][j] >= 0 and v still live
+ *       x[v] = x[v] - w[s][j] * x[s]
+ *     the product and the difference rounded separately.  (Scores may be negative: the message
+ *     then raises the neighbour; nothing special happens.)
+ *   Unfilled tail entries of picked are -1 and of value -1.
+ *   bad[0] += the rows with a NaN or infinite x, the rows with a group outside [0, G), and the
+ *   messages that left a neighbour's score non-finite (the caller clears it, and rejects the
+ *   call's results when it is non-zero; such rows are treated as retired, so the loop ends on any
+ *   input).
+ *
+ *   ONE persistent workgroup of 1024 threads runs the whole loop: no launch per pick, no grid-wide
+ *   wait, no waiting on another workgroup, workgroup barriers only.  The scores stay in the
+ *   workspace (L2-resident); LDS holds the maximum of every DD_D2_BLOCK_ROWS consecutive rows, the
+ *   maximum of every 64 of those, and the groups' remaining quotas.  A pick walks top -> block ->
+ *   row on one wave, sends the k messages from k lanes of that wave, and one wave per touched block
+ *   (k + 1 at most) recomputes that block's maximum.
+ *
+ * Invariance: there is exactly one workgroup and every step above is defined by the inputs (the
+ * maxima are exact, the ties go by index, the messages apply in slot order), so the outcome
+ * depends on the inputs alone, never on a launch geometry.
+ *
+ * Limits (all three): 0 <= n <= DD_D2_MAX_ROWS (2^21: 128 x 64 blocks of DD_D2_BLOCK_ROWS rows;
+ * their maxima take 32 KiB of the workgroup's LDS), 1 <= k <= DD_KNN_MAX_K; dd_d2_select also
+ * 1 <= G <= DD_D2_MAX_GROUPS (the quotas take 4 G bytes of LDS beside them) and 0 <= total <= n.
+ * Outside them, a NULL buffer the call would touch, or a workspace below dd_d2_workspace_bytes
+ * (host only; 0 for bad arguments; 4 n rounded up to whole blocks plus 4 bytes per block, each
+ * region rounded up to 256) or not 16-byte aligned is DD_EINVAL with a message before any launch.
+ * n == 0 returns DD_OK.  No allocation, no synchronisation inside (graph-capturable); everything
+ * on `stream`; plain vector stores and one int32 atomic counter (bad) only.
+ * ---------------------------------------------------------------------------------------- */
+#define DD_D2_MAX_ROWS 2097152
+#define DD_D2_MAX_GROUPS 16384
+#define DD_D2_BLOCK_ROWS 256
+
+int dd_d2_weights(const float* dist, const int64_t* nbr_id, int64_t n, int32_t k, float coef,
+                  float* w, void* stream);
+
+int dd_d2_propagate(const float* x0, const int64_t* nbr_id, const float* w, int64_t n, int32_t k,
+                    float* x1, int32_t* bad, void* stream);
+
+size_t dd_d2_workspace_bytes(int64_t n, int32_t G);
+
+int dd_d2_select(const float* x, const int64_t* nbr_id, const float* w, const int64_t* group,
+                 const int64_t* quota, int64_t n, int32_t k, int32_t G, int64_t total,
+                 int64_t* picked, float* value, int32_t* bad, void* workspace,
+                 size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------- *
  * Distance to the nearest k-means centroid in feature space: the self-supervised prototype
  * distance of Sorscher et al. ("Beyond neural scaling laws"), which needs no labels.  Purely
  * additive: dd_abi_version() stays 10.
