@@ -10,6 +10,7 @@ from __future__ import annotations
 import ctypes
 import itertools
 import math
+import numbers
 import os
 import threading
 
@@ -49,6 +50,7 @@ EXPORTS = (
     "dd_class_feature_sums", "dd_class_centroids", "dd_proto_scores",
     "dd_nn_workspace_bytes", "dd_nn_same_class",
     "dd_knn_workspace_bytes", "dd_knn",
+    "dd_kde_workspace_bytes", "dd_kde",
     "dd_kcenter_workspace_bytes", "dd_kcenter_seed_batch", "dd_kcenter_greedy",
     "dd_kmedoids_workspace_bytes", "dd_kmedoids_greedy",
     "dd_d2_weights", "dd_d2_propagate", "dd_d2_workspace_bytes", "dd_d2_select",
@@ -111,6 +113,9 @@ def lib():
                 "dd_knn_workspace_bytes": (SZ, [I64, I64, I32, I32, I32, I32]),
                 "dd_knn": (I32, [P, P, P, I64, P, P, P, I64, I32, I32, I32, I32, P, P, P, P, P,
                                  P, P, SZ, P]),
+                "dd_kde_workspace_bytes": (SZ, [I64, I64, I32, I64, I32]),
+                "dd_kde": (I32, [P, P, P, I64, P, P, P, I64, I32, F32, I64, I32, P, P, P, P, P,
+                                 SZ, P]),
                 "dd_kcenter_workspace_bytes": (SZ, [I64, I32, I32, I64]),
                 "dd_kcenter_seed_batch": (I32, [I32, I32]),
                 "dd_kcenter_greedy": (I32, [P, P, I64, I32, P, I32, P, P, I64, P, I64, I32, I32,
@@ -647,6 +652,78 @@ def knn(q: torch.Tensor, q_id: torch.Tensor, c: torch.Tensor, c_id: torch.Tensor
     _check(rc, "dd_knn")
     # the fp32 rows read twice (pack, value), the halves written once
     _t1(e0, "el2n", (nq + nc) * (8.0 * D + 4.0 * Dp), q)
+    return workspace
+
+
+# ---- kernel density over all rows, and the Parzen posterior of the own label --------------------
+KDE_MAX_SEGMENTS = 64
+
+
+def kde_workspace_bytes(nq: int, nc: int, D: int, seg_rows: int = 0,
+                        operands: str = "f16x3") -> int:
+    """Bytes of kde's workspace for the same `seg_rows` (dd_kde_workspace_bytes; 0 for sizes
+    outside the entry point's limits)."""
+    return int(lib().dd_kde_workspace_bytes(int(nq), int(nc), int(D), int(seg_rows),
+                                            OPERANDS[operands]))
+
+
+def kde(q: torch.Tensor, q_id: torch.Tensor, c: torch.Tensor, c_id: torch.Tensor, inv: float, *,
+        q_label=None, c_label=None, seg_rows: int = 0, operands: str = "f16x3", nll=None,
+        post=None, accum_nll=None, accum_post=None, workspace=None):
+    """Per row of q [nq, D], over the rows j of c [nc, D] whose c_id differs from the row's q_id,
+    with the weights w_j = exp(-||q - c_j||^2 inv) (dd_kde).  Writes whichever are given of nll
+    fp32 [nq] (-ln sum_j w_j), post fp32 [nq] (ln sum_j w_j - ln of the sum over the rows whose
+    c_label equals the row's q_label; both int64 label vectors are then required) and the
+    accumulators accum_nll / accum_post fp32 [nq] (+=).  Without a candidate nll is +inf, without
+    one of the row's label post is +inf; NaN for a non-finite query row.  inv: a finite float
+    > 0.  seg_rows: candidates per segment, a multiple of 128 (0: chosen from nc alone; the sums'
+    last bits depend on it).  workspace: a uint8 tensor of kde_workspace_bytes, or None to
+    allocate one.  Returns the workspace."""
+    if (isinstance(inv, bool) or not isinstance(inv, numbers.Real)
+            or not 0.0 < float(inv) < float("inf")):
+        raise ValueError(f"kde: inv must be a finite number > 0 (got {inv!r})")
+    seg_rows = int(seg_rows)
+    if seg_rows < 0 or seg_rows % 128:
+        raise ValueError(f"kde: seg_rows must be 0 or a multiple of 128 (got {seg_rows})")
+    outs = (nll, post, accum_nll, accum_post)
+    if all(o is None for o in outs):
+        raise ValueError("kde: no output requested")
+    labelled = post is not None or accum_post is not None
+    if labelled and (q_label is None or c_label is None):
+        raise ValueError("kde: post / accum_post need q_label and c_label")
+    code = _operands_code(operands)
+    _dev(q, torch.float32, "q", 2)
+    _dev(c, torch.float32, "c", 2)
+    nq, D = q.shape
+    nc = c.shape[0]
+    if c.shape[1] != D:
+        raise ValueError(f"c must be [nc, {D}] (got {tuple(c.shape)})")
+    if seg_rows and -(-nc // seg_rows) > KDE_MAX_SEGMENTS:
+        raise ValueError(f"kde: at most {KDE_MAX_SEGMENTS} segments (nc={nc}, "
+                         f"seg_rows={seg_rows})")
+    need = int(lib().dd_kde_workspace_bytes(nq, nc, D, seg_rows, code))
+    if need == 0:
+        raise ValueError(f"kde: unsupported size nq={nq}, nc={nc}, D={D}")
+    if workspace is None or workspace.numel() * workspace.element_size() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=q.device)
+    ptrs = [_opt(nll, torch.float32, "nll", nq), _opt(post, torch.float32, "post", nq),
+            _opt(accum_nll, torch.float32, "accum_nll", nq),
+            _opt(accum_post, torch.float32, "accum_post", nq)]
+    labs = [_opt(q_label if labelled else None, torch.int64, "q_label", nq),
+            _opt(c_label if labelled and nc else None, torch.int64, "c_label", nc)]
+    if nq == 0:  # nothing to do (and an empty tensor's pointer is NULL: "not requested")
+        return workspace
+    Dp = (D + 15) // 16 * 16
+    e0 = _t0(q, always=True)
+    rc = lib().dd_kde(
+        _dev(q, torch.float32, "q"), _opt(q_id, torch.int64, "q_id", nq), labs[0], nq,
+        _opt(c if nc else None, torch.float32, "c"),
+        _opt(c_id if nc else None, torch.int64, "c_id", nc), labs[1], nc, D, float(inv),
+        seg_rows, code, *ptrs, _dev(workspace, torch.uint8, "workspace"),
+        workspace.numel() * workspace.element_size(), _stream(q))
+    _check(rc, "dd_kde")
+    # the fp32 rows read once (pack), the halves written once
+    _t1(e0, "el2n", (nq + nc) * (4.0 * D + 4.0 * Dp), q)
     return workspace
 
 

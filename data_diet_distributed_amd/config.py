@@ -22,13 +22,16 @@ DEFAULTS = {
     # with another label, scoring.KNN_METHODS) | kmeans (the distance to the nearest centroid of
     # a k-means clustering of the feature rows: the prototype distance without labels,
     # scoring.CLUSTER_METHODS) | maha (the Mahalanobis distance to the class mean under the tied
-    # within-class covariance of the feature rows, scoring.COVARIANCE_METHODS); select_by takes any
+    # within-class covariance of the feature rows, scoring.COVARIANCE_METHODS) | kde, kde_post (the
+    # negative log kernel density among all feature rows and the negative log Parzen posterior of
+    # the own label, scoring.DENSITY_METHODS); select_by takes any
     "score_methods": ["el2n"],
     "select_by": "el2n",
     "knn_k": 5,                       # neighbours of knn / knn_disagree (1..16)
     "kmeans_k": 0,                    # clusters of kmeans (0: num_classes; at most 4096)
     "kmeans_iters": 20,               # Lloyd updates of kmeans per checkpoint (1..1000)
     "maha_shrink": 0.01,              # shrinkage of maha's covariance to its mean eigenvalue [0, 1]
+    "kde_bandwidth": 0.25,            # kde / kde_post: bandwidth^2 over the mean squared distance (> 0)
     "select_policy": "global",        # global (reference) | stratified | balanced class quotas
     "select_skip": 0,                 # ranks skipped from the top before the k kept ones
     "select_fill": "score",           # score (the rank cut) | kcenter (coverage: greedy k-center)

@@ -1,25 +1,27 @@
 """The consumers of the EL2N pass's train-BN forward: LogitScores (el2n + LOGIT_METHODS, from
-each launch's logits), ProtoScore, KMeansScore, NNScore, KNNScore and MahaScore (from the
-checkpoint's pooled feature rows, over every rank), and ForwardScores, which holds the requested
-ones for one score_shard call.
+each launch's logits), ProtoScore, KMeansScore, NNScore, KNNScore, KDEScore and MahaScore (from
+the checkpoint's pooled feature rows, over every rank), and ForwardScores, which holds the
+requested ones for one score_shard call.
 
 The pass hands every launch's logits to `consume` and, when `features` is not None, writes the
 launch's feature rows there; after a checkpoint's last chunk it calls `end_checkpoint`.  Every
 rank issues its collectives in the same order: the counts all-reduce (proto) and the lengths and
-labels all-gathers (nn, the knn scores and maha: one of each, shared, GatheredRows; kmeans alone
-takes the lengths only) at construction, then per checkpoint the proto all-reduce, the kmeans
-all-reduces (the seed rows, then one per Lloyd iteration) and last the one all-gather of the
-feature rows that nn, the knn scores and maha share.
+labels all-gathers (nn, the knn scores, the density scores and maha: one of each, shared,
+GatheredRows; kmeans alone takes the lengths only) at construction, then per checkpoint the
+proto all-reduce, the kmeans all-reduces (the seed rows, then one per Lloyd iteration) and last
+the one all-gather of the feature rows that nn, the knn scores, the density scores and maha
+share.
 """
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional
 
 import torch
 
 from . import _capi
 from .collectives import _all_reduce_sum, gather_rows, shard_lengths, world_of
-from .methods import KNN_METHODS, LOGIT_FAMILY
+from .methods import DENSITY_METHODS, KNN_METHODS, LOGIT_FAMILY
 
 
 def check_class_sizes(largest: int):
@@ -30,13 +32,13 @@ def check_class_sizes(largest: int):
                          f"hold fewer than {_capi.PROTO_MAX_CLASS} (2^24) per class")
 
 
-def check_no_singleton_class(counts):
-    """The nn score of a class's only member would be infinite (no other row of its class):
-    reject a dataset with such a class, naming it.  counts: members per class over the whole
-    dataset (an empty class is fine)."""
+def check_no_singleton_class(counts, what="nn"):
+    """The nn score of a class's only member would be infinite (no other row of its class), and
+    so would its kde_post (`what` names the score): reject a dataset with such a class, naming
+    it.  counts: members per class over the whole dataset (an empty class is fine)."""
     for c, m in enumerate(counts):
         if int(m) == 1:
-            raise ValueError(f"nn: class {c} has exactly one member in the whole dataset; its "
+            raise ValueError(f"{what}: class {c} has exactly one member in the whole dataset; its "
                              f"nearest same-class neighbour does not exist (score +inf)")
 
 
@@ -97,6 +99,55 @@ def nearest_k(features: torch.Tensor, labels: torch.Tensor, num_classes: int, k:
     _capi.knn(features, ids, features, ids, k, q_label=labels, c_label=labels, operands=operands,
               mean_dist=mean, disagree=share)
     return mean, share
+
+
+KDE_SCALE_ROWS = 1 << 16  # rows per float64 block of kde_scale (fixed: the order is part of s)
+
+
+def kde_scale(rows: torch.Tensor) -> float:
+    """s of the density scores: the mean squared distance over all ordered pairs of distinct rows
+    of `rows` [N, D], s = 2 N / (N - 1) (mean ||f||^2 - ||mean f||^2), in float64 over fixed
+    blocks of rows in the order given (a function of the rows and their order alone; one read
+    back).  A row with a non-finite element, which the kernel ignores as a candidate, is left
+    out, N counting the others.  Raises ValueError where no positive scale exists (fewer than two
+    finite rows, or all of them equal)."""
+    D = rows.shape[1]
+    acc = torch.zeros(D + 2, dtype=torch.float64, device=rows.device)  # sum f, sum ||f||^2, N
+    for r0 in range(0, rows.shape[0], KDE_SCALE_ROWS):
+        x = rows[r0:r0 + KDE_SCALE_ROWS].double()
+        ok = torch.isfinite(x).all(dim=1)
+        x = torch.where(ok[:, None], x, torch.zeros_like(x))
+        acc[:D] += x.sum(dim=0)
+        acc[D] += (x * x).sum()
+        acc[D + 1] += ok.sum()
+    host = acc.cpu()
+    N = float(host[D + 1])
+    if N < 2:
+        raise ValueError(f"kde: needs at least two finite feature rows (got {int(N)})")
+    s = 2.0 * N / (N - 1.0) * (float(host[D]) / N - float((host[:D] / N).square().sum()))
+    if not 0.0 < s < float("inf"):
+        raise ValueError(f"kde: the feature rows have no positive mean squared distance (s={s})")
+    return s
+
+
+def density(features: torch.Tensor, labels: torch.Tensor, num_classes: int, bandwidth: float,
+            operands: str = "f16x3"):
+    """(kde fp32 [n], kde_post fp32 [n]): each row's negative log kernel density among the other
+    rows of `features` [n, D] and the negative log Parzen posterior of its own label, the weights
+    exp(-d^2 / (bandwidth s)) with s = kde_scale(features) (one dd_kde launch).  Raises LabelError
+    for a label outside [0, C) and ValueError for a class of exactly one member."""
+    from .methods import check_bandwidth
+    bandwidth = check_bandwidth(bandwidth)
+    labels = labels.contiguous()
+    counts, _ = _capi.class_counts(labels, num_classes, check=True)
+    check_no_singleton_class(counts.tolist(), "kde_post")
+    n = features.shape[0]
+    ids = torch.arange(n, dtype=torch.int64, device=features.device)
+    nll = torch.empty(n, dtype=torch.float32, device=features.device)
+    post = torch.empty_like(nll)
+    _capi.kde(features, ids, features, ids, 1.0 / (bandwidth * kde_scale(features)),
+              q_label=labels, c_label=labels, operands=operands, nll=nll, post=post)
+    return nll.add_(math.log(max(n - 1, 1))), post
 
 
 def kmeans_seed_rows(N: int, k: int) -> List[int]:
@@ -463,6 +514,53 @@ class KNNScore:
         return {m: ensemble_mean(a, K) for m, a in self.acc.items()}
 
 
+class KDEScore:
+    """The per-call state of the density scores (`methods`: those requested among DENSITY_METHODS)
+    for the shard's `labels` [n], built once and reused by every checkpoint.  Queries, candidates,
+    ids and labels as KNNScore's; `bad` is this shard's count of labels outside [0, C).  With
+    kde_post the whole dataset's class counts are read to the host once: a class of exactly one
+    member is rejected by name.  Holds the accumulators (of -ln sum w and of kde_post) and the
+    kernel's workspace (4 (n + N) pad16(D) + 4 (n + N) + 16 n segments bytes).  Every rank
+    computes the scale s from ALL the gathered rows in dataset order (kde_scale: one read back
+    per checkpoint), so the scores do not depend on the chunk size, the lanes or the world
+    size."""
+
+    def __init__(self, methods, labels: torch.Tensor, linear, rows: GatheredRows, operands: str,
+                 bandwidth: float):
+        n, dev = labels.numel(), labels.device
+        C, D = linear.out_features, linear.in_features
+        _check_width("kde", D)
+        self.N = sum(rows.lengths)
+        self.operands, self.bandwidth = operands, float(bandwidth)
+        _, self.bad = _capi.class_counts(labels, C, check=False)
+        self.q_id = torch.arange(n, dtype=torch.int64, device=dev) + rows.offset
+        self.c_id = (self.q_id if rows.local
+                     else torch.arange(self.N, dtype=torch.int64, device=dev))
+        self.q_label, self.c_label = labels, rows.labels.contiguous()
+        if "kde_post" in methods:
+            counts, _ = _capi.class_counts(self.c_label, C, check=False)
+            check_no_singleton_class(counts.tolist(), "kde_post")  # the one read of the counts
+        self.acc = {m: torch.zeros(n, dtype=torch.float32, device=dev) for m in methods}
+        need = _capi.kde_workspace_bytes(n, self.N, D, 0, operands)
+        self.workspace = torch.empty(max(need, 1), dtype=torch.uint8, device=dev)
+
+    def end_checkpoint(self, features: torch.Tensor, allf: torch.Tensor):
+        """At the same point of a checkpoint as NNScore's, on the same gathered rows `allf`: the
+        scale, then one dd_kde launch that accumulates the requested scores."""
+        inv = 1.0 / (self.bandwidth * kde_scale(allf))
+        self.workspace = _capi.kde(
+            features, self.q_id, allf, self.c_id, inv, q_label=self.q_label,
+            c_label=self.c_label, operands=self.operands, accum_nll=self.acc.get("kde"),
+            accum_post=self.acc.get("kde_post"), workspace=self.workspace)
+
+    def finalize(self, K: int) -> Dict[str, torch.Tensor]:
+        """The ensemble means; kde = ln(N - 1) - ln sum w: the constant is added once."""
+        out = {m: ensemble_mean(a, K) for m, a in self.acc.items()}
+        if "kde" in out:
+            out["kde"] = out["kde"] + math.log(max(self.N - 1, 1))
+        return out
+
+
 class MahaScore:
     """The per-call state of the maha score for the shard's `labels` [n], built once and reused by
     every checkpoint: every rank's labels (`rows`), their class counts (`bad` is this shard's
@@ -531,17 +629,21 @@ class ForwardScores:
         self.kcenter_ckpt, self.kcenter_rows, self._ckpts_done = kcenter_ckpt, None, 0
         logit = [m for m in methods if m in LOGIT_FAMILY]
         self.logit = LogitScores(logit, n, labels.device) if logit else None
-        self.proto = self.kmeans = self.nn = self.knn = self.maha = self.rows = None
+        self.proto = self.kmeans = self.nn = self.knn = self.maha = self.kde = self.rows = None
         if "proto" in methods:
             self.proto = ProtoScore(labels, linear, group, cfg.batch_size)
         knn = [m for m in methods if m in KNN_METHODS]
-        if "nn" in methods or knn or "maha" in methods or kcenter_ckpt is not None:
+        kde = [m for m in methods if m in DENSITY_METHODS]
+        if "nn" in methods or knn or kde or "maha" in methods or kcenter_ckpt is not None:
             labels = labels.contiguous()
             self.rows = GatheredRows(labels, group)
         if "nn" in methods:
             self.nn = NNScore(labels, linear, self.rows, cfg.el2n_operands)
         if knn:
             self.knn = KNNScore(knn, labels, linear, self.rows, cfg.el2n_operands, cfg.knn_k)
+        if kde:
+            self.kde = KDEScore(kde, labels, linear, self.rows, cfg.el2n_operands,
+                                cfg.kde_bandwidth)
         if "maha" in methods:
             self.maha = MahaScore(labels, linear, self.rows, cfg.el2n_operands, cfg.maha_shrink,
                                   self.proto)
@@ -553,7 +655,8 @@ class ForwardScores:
         # the one [n, D] fp32 buffer of the checkpoint's feature rows (n D 4 bytes: 102 MB at
         # 50 000 x 512, 10.5 GB for 1.28 M x 2048 rows on one rank), or None: logits only
         self.features = None
-        by_features = self.proto or self.nn or self.knn or self.kmeans or self.maha
+        by_features = (self.proto or self.nn or self.knn or self.kde or self.kmeans
+                       or self.maha)
         if kcenter_ckpt is not None:
             _check_width("d2" if cfg.select_diversity == "d2" else "kcenter", linear.in_features)
         if by_features or kcenter_ckpt is not None:
@@ -581,7 +684,7 @@ class ForwardScores:
         # one all-gather of the rows serves nn, the knn scores, maha and the kcenter fill (which
         # alone needs it at its one checkpoint only)
         if self.rows is not None and (keep or self.nn is not None or self.knn is not None
-                                      or self.maha is not None):
+                                      or self.kde is not None or self.maha is not None):
             allf = self.rows.gather(self.features)
             if keep:
                 # (one rank: `allf` is the feature buffer itself, which the next checkpoint
@@ -591,13 +694,15 @@ class ForwardScores:
                 self.nn.end_checkpoint(self.features, allf)
             if self.knn is not None:
                 self.knn.end_checkpoint(self.features, allf)
+            if self.kde is not None:
+                self.kde.end_checkpoint(self.features, allf)
             if self.maha is not None:
                 self.maha.end_checkpoint(self.features, allf)
         self._ckpts_done += 1
 
     def _parts(self):
-        return [p for p in (self.logit, self.proto, self.nn, self.knn, self.kmeans, self.maha)
-                if p is not None]
+        return [p for p in (self.logit, self.proto, self.nn, self.knn, self.kde, self.kmeans,
+                            self.maha) if p is not None]
 
     def tensors(self) -> List[torch.Tensor]:
         """Every device buffer the pass and the second phase touch (for the streams'

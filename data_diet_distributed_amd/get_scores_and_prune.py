@@ -44,18 +44,20 @@ from .synthetic import state_digest
 
 
 # from the rows the classifier consumes
-FEATURE_SCORES = ("nn", "knn", "knn_disagree", "kmeans", "maha")
+FEATURE_SCORES = ("nn", "knn", "knn_disagree", "kmeans", "maha", "kde", "kde_post")
 
 
 def _feature_scores(feats, labels, num_classes, score, knn_k, kmeans_k=0, kmeans_iters=20,
-                    maha_shrink=0.01):
+                    maha_shrink=0.01, kde_bandwidth=0.25):
     """The chosen score of FEATURE_SCORES among the visited rows `feats` [n, D] (LabelError for
     a label outside [0, C))."""
-    from .forward_scores import kmeans, maha, nearest_k, nearest_same_class
+    from .forward_scores import density, kmeans, maha, nearest_k, nearest_same_class
     if score == "nn":
         return nearest_same_class(feats, labels, num_classes)
     if score == "maha":
         return maha(feats, labels, num_classes, maha_shrink)
+    if score in ("kde", "kde_post"):
+        return density(feats, labels, num_classes, kde_bandwidth)[score == "kde_post"]
     if score == "kmeans":
         _capi.class_counts(labels.contiguous(), num_classes, check=True)
         return kmeans(feats, int(kmeans_k) or num_classes, kmeans_iters)[2]
@@ -75,14 +77,16 @@ def _score_rows(logits, labels, out, bad, score="el2n"):
 
 def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect=None,
                             score="el2n", knn_k=5, keep_rows=False, kmeans_k=0, kmeans_iters=20,
-                            maha_shrink=0.01):
+                            maha_shrink=0.01, kde_bandwidth=0.25):
     """Scores of every example the loader yields, in visit order, plus the visited indices
     (`score`: "el2n" or one of _capi.LOGIT_STATS, from the same logits; or "nn", the distance to
     the nearest visited example of the same class, or "knn" / "knn_disagree", the mean distance
     to the knn_k nearest visited examples and the share of them with another label, or "kmeans",
     the distance to the nearest of kmeans_k centroids of the visited examples after kmeans_iters
     Lloyd updates, or "maha", the Mahalanobis distance to the class mean under the visited
-    examples' tied covariance shrunk by maha_shrink, from the rows `net.linear` consumes).
+    examples' tied covariance shrunk by maha_shrink, or "kde" / "kde_post", the negative log kernel
+    density among the visited examples and the negative log Parzen posterior of the own label at
+    bandwidth kde_bandwidth, from the rows `net.linear` consumes).
     A dict given as `collect` receives "labels" (the targets in visit order, int64 on the
     device) and "num_classes" (the width of the logits), for the class selection policies, and
     with keep_rows "rows": the rows `net.linear` consumes, in visit order (the kcenter fill).
@@ -123,7 +127,7 @@ def el2n_scores_from_loader(train_loader, net, device, num_classes=None, collect
             hook.remove()
     if by_rows and visit:
         scores = [_feature_scores(torch.cat(feats).contiguous(), torch.cat(targets), C, score,
-                                  knn_k, kmeans_k, kmeans_iters, maha_shrink)]
+                                  knn_k, kmeans_k, kmeans_iters, maha_shrink, kde_bandwidth)]
     if collect is not None and keep_rows:
         collect["rows"] = torch.cat(feats).contiguous() if feats else None
     if collect is not None:
@@ -327,7 +331,8 @@ def fast_path(train_loader, net, device):
 
 
 def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, score="el2n",
-                     knn_k=5, collect=None, kmeans_k=0, kmeans_iters=20, maha_shrink=0.01):
+                     knn_k=5, collect=None, kmeans_k=0, kmeans_iters=20, maha_shrink=0.01,
+                     kde_bandwidth=0.25):
     """Scores in visit order + visited indices, like el2n_scores_from_loader, on the hand
     kernels: every visit batch of the loader's BatchSampler (all of size B but a ragged last
     one) is one BN group; chunks of whole batches are gathered + normalised on device.  A dict
@@ -381,7 +386,8 @@ def el2n_scores_fast(train_loader, src, model, device, chunk_rows: int = 1024, s
             _score_rows(logits.contiguous(), lab_d[idx], scores[c0:c1], bad, score)
         if by_rows:  # neighbours among the visited examples (LabelError inside)
             return _feature_scores(feats, lab_d[visit_d], model.linear.out_features, score,
-                                   knn_k, kmeans_k, kmeans_iters, maha_shrink), visit_d
+                                   knn_k, kmeans_k, kmeans_iters, maha_shrink,
+                                   kde_bandwidth), visit_d
     # a label outside [0, C): the reference's one_hot raises (:17), so does this path
     _capi.check_labels(bad, model.linear.out_features, "sparse_loader")
     return scores, visit_d
@@ -434,7 +440,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                   fast: bool = True, refine="auto", policy="global", skip=0, score="el2n",
                   knn_k=5, fill="score", seed_frac=0.0, kmeans_k=0, kmeans_iters=20,
                   objective="radius", maha_shrink=0.01, diversity="none", d2_k=10,
-                  d2_gamma_f=1.0, d2_gamma_r=1.0):
+                  d2_gamma_f=1.0, d2_gamma_r=1.0, kde_bandwidth=0.25):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
@@ -463,6 +469,11 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     "maha" ranks by the Mahalanobis distance to the class mean under the tied within-class
     covariance of the visited examples' rows, shrunk by maha_shrink in [0, 1] towards its mean
     eigenvalue (dd_maha_scatter / dd_maha_dist; a covariance without a Cholesky factor raises).
+    "kde" ranks by the negative log kernel density among the visited examples' rows, every other
+    visited example voting with the weight exp(-d^2 / (kde_bandwidth s)), s the mean squared
+    distance between the rows, and "kde_post" by the negative log Parzen posterior of the own
+    label under the same weights (dd_kde; kde_bandwidth finite and > 0; with "kde_post" a class
+    with exactly one visited member raises).
     fill / seed_frac: how the quotas are filled (ScoreConfig.select_fill / kcenter_seed_frac):
     "score" is the rank cut; "kcenter" seeds every group with its top
     max(1, floor(seed_frac * quota)) examples by `score` and picks the rest by farthest-first
@@ -483,7 +494,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
     over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
     score="el2n"."""
-    from .methods import check_diversity, check_objective, check_selection, check_shrink
+    from .methods import (check_bandwidth, check_diversity, check_objective, check_selection,
+                          check_shrink)
     from .scoring import normalize_refine, select_with_policy
     refine = normalize_refine(refine)
     if score in ("variability", "grand", "proto"):
@@ -503,6 +515,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                 raise ValueError(f"{name} must be an integer in {lo}..{hi} (got {v!r})")
     if score == "maha":
         maha_shrink = check_shrink(maha_shrink)
+    if score in ("kde", "kde_post"):
+        kde_bandwidth = check_bandwidth(kde_bandwidth)
     if refine is True and score != "el2n":
         raise ValueError("refine=True re-scores EL2N only: it needs score='el2n'")
     skip = check_selection(policy, skip, "policy", "skip", fill=fill, seed_frac=seed_frac,
@@ -529,14 +543,16 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     if fp is not None:
         scores, visit = el2n_scores_fast(train_loader, fp[0], fp[1], device, score=score,
                                          knn_k=knn_k, collect=seen, kmeans_k=kmeans_k,
-                                         kmeans_iters=kmeans_iters, maha_shrink=maha_shrink)
+                                         kmeans_iters=kmeans_iters, maha_shrink=maha_shrink,
+                                         kde_bandwidth=kde_bandwidth)
     else:
         if policy != "global":  # a class policy needs the visited targets
             seen = {}
         scores, visit = el2n_scores_from_loader(train_loader, net, device, collect=seen,
                                                 score=score, knn_k=knn_k, keep_rows=kcenter,
                                                 kmeans_k=kmeans_k, kmeans_iters=kmeans_iters,
-                                                maha_shrink=maha_shrink)
+                                                maha_shrink=maha_shrink,
+                                                kde_bandwidth=kde_bandwidth)
     samples = _capi.keep_count(train_samples, sparsity)
     if samples < 0 or samples > scores.numel():
         raise ValueError(f"keep count {samples} outside [0, {scores.numel()}]")
@@ -582,6 +598,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                             **({"kmeans_k": int(kmeans_k) or int(module.linear.out_features),
                                 "kmeans_iters": int(kmeans_iters)} if score == "kmeans" else {}),
                             **({"maha_shrink": float(maha_shrink)} if score == "maha" else {}),
+                            **({"kde_bandwidth": float(kde_bandwidth)}
+                               if score in ("kde", "kde_post") else {}),
                             **({} if default_rule else {
                                 "select_policy": policy, "select_skip": int(skip),
                                 "class_quota": sparse_loader.last_selection["class_quota"],

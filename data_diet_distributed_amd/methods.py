@@ -50,19 +50,31 @@ CLUSTER_METHODS = ("kmeans",)
 # forms S from all the rows in dataset order, so the scores are bitwise independent of chunks,
 # lanes and ranks (include/dd_capi.h dd_maha_scatter).
 COVARIANCE_METHODS = ("maha",)
+# The soft form of the KNN_METHODS, from the same feature rows over the WHOLE dataset: every other
+# row votes with the weight w_ij = exp(-|| f_i - f_j ||^2 / (tau s)), tau = ScoreConfig.
+# kde_bandwidth, s = the mean squared distance over all ordered pairs of distinct rows:
+#   kde_i      = ln(N - 1) - ln sum_{j != i} w_ij (the negative log kernel density: coreset
+#                density weighting; needs no labels)
+#   kde_post_i = ln sum_{j != i} w_ij - ln sum_{j != i, y_j = y_i} w_ij (the negative log Parzen-
+#                window posterior of the row's own label: knn_disagree with every row voting)
+# Larger = more isolated / more suspicious.  No k and no hard cut (dd_kde: a streaming
+# log-sum-exp over all N rows per row).
+DENSITY_METHODS = ("kde", "kde_post")
 
 
 def known(method: str) -> bool:
     return (method == "grand" or method in FORWARD_SCORES or method in KNN_METHODS
-            or method in CLUSTER_METHODS or method in COVARIANCE_METHODS)
+            or method in CLUSTER_METHODS or method in COVARIANCE_METHODS
+            or method in DENSITY_METHODS)
 
 
 def pass_of(method: str) -> str:
     """The pass that computes `method`: "el2n" (the shared forward of the logit family, the
-    feature scores, the neighbour scores, the cluster score and the covariance score) or
-    "grand"."""
+    feature scores, the neighbour scores, the cluster score, the covariance score and the density
+    scores) or "grand"."""
     return ("el2n" if method in FORWARD_SCORES or method in KNN_METHODS
-            or method in CLUSTER_METHODS or method in COVARIANCE_METHODS else "grand")
+            or method in CLUSTER_METHODS or method in COVARIANCE_METHODS
+            or method in DENSITY_METHODS else "grand")
 
 
 def check_shrink(shrink, name="maha_shrink") -> float:
@@ -72,6 +84,16 @@ def check_shrink(shrink, name="maha_shrink") -> float:
             or not 0.0 <= float(shrink) <= 1.0):
         raise ValueError(f"{name} must be a number in [0, 1] (got {shrink!r})")
     return float(shrink)
+
+
+def check_bandwidth(bandwidth, name="kde_bandwidth") -> float:
+    """ScoreConfig's kde_bandwidth, and sparse_loader's under its own name: a finite number > 0
+    (returned as a float)."""
+    if (isinstance(bandwidth, bool)
+            or not isinstance(bandwidth, (int, float, np.integer, np.floating))
+            or not 0.0 < float(bandwidth) < float("inf")):
+        raise ValueError(f"{name} must be a finite number > 0 (got {bandwidth!r})")
+    return float(bandwidth)
 
 
 def refinable(method: str) -> bool:

@@ -15,7 +15,9 @@ rest (config.DEFAULTS):
                      wrong_mass | variability (needs K >= 2 to rank by), and proto (the
                      distance of the pooled feature row to its class mean, same forward)
                      and nn (its distance to the nearest other row of the same class: a
-                     near-duplicate scores close to 0 and is dropped first)
+                     near-duplicate scores close to 0 and is dropped first), and kde / kde_post
+                     (the negative log kernel density among all rows and the negative log Parzen
+                     posterior of the own label; kde_bandwidth, --kde-bandwidth)
   score_checkpoints  K: checkpoint_path/seed{k}/ckpt_{score_epoch}.pth (K = 1: ckpt_E.pth)
   select_policy      global (reference) | stratified | balanced: per-class quotas (--policy)
   select_skip        ranks skipped from the top before the kept window (--skip)
@@ -149,6 +151,7 @@ def engine_config(cfg):
                        kmeans_k=int(cfg.get("kmeans_k", 0)),
                        kmeans_iters=int(cfg.get("kmeans_iters", 20)),
                        maha_shrink=cfg.get("maha_shrink", 0.01),
+                       kde_bandwidth=cfg.get("kde_bandwidth", 0.25),
                        select_fill=str(cfg.get("select_fill", "score")),
                        kcenter_seed_frac=float(cfg.get("kcenter_seed_frac", 0.0)),
                        kcenter_ckpt=int(cfg.get("kcenter_ckpt", -1)),
@@ -209,6 +212,8 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
             meta.update(kmeans_k=int(ecfg.kmeans_k) or ncls, kmeans_iters=int(ecfg.kmeans_iters))
         if "maha" in ecfg.methods:
             meta["maha_shrink"] = float(ecfg.maha_shrink)
+        if any(m in ("kde", "kde_post") for m in ecfg.methods):
+            meta["kde_bandwidth"] = float(ecfg.kde_bandwidth)
         sel = eng.last_selection
         if sel["policy"] != "global" or sel["skip"]:  # (a default run's metadata is unchanged)
             meta.update(select_policy=sel["policy"], select_skip=sel["skip"],
@@ -264,15 +269,20 @@ def parse(argv=None):
                     help="sharpness of the forward edge weights (default: d2_gamma_f)")
     ap.add_argument("--d2-gamma-r", type=float, default=None,
                     help="sharpness of the reverse edge weights (default: d2_gamma_r)")
+    ap.add_argument("--kde-bandwidth", type=float, default=None,
+                    help="bandwidth of the kde / kde_post scores (default: kde_bandwidth of the "
+                         "config)")
     return ap.parse_args(argv)
 
 
 def apply_overrides(cfg: dict, args) -> dict:
-    """The command line's selection options written over the config's keys (in place)."""
+    """The command line's selection and score options written over the config's keys (in
+    place)."""
     for key, v in (("select_policy", args.policy), ("select_skip", args.skip),
                    ("select_fill", args.fill), ("kcenter_objective", args.fill_objective),
                    ("select_diversity", args.diversity), ("d2_k", args.d2_k),
-                   ("d2_gamma_f", args.d2_gamma_f), ("d2_gamma_r", args.d2_gamma_r)):
+                   ("d2_gamma_f", args.d2_gamma_f), ("d2_gamma_r", args.d2_gamma_r),
+                   ("kde_bandwidth", args.kde_bandwidth)):
         if v is not None:
             cfg[key] = v
     return cfg

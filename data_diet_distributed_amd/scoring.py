@@ -48,9 +48,11 @@ from .collectives import (_all_reduce_sum, _world, all_shards, gather_padded,  #
                           gather_rows, gather_scores, shard_bounds, shard_lengths, world_of)
 from .forward_scores import (ForwardScores, check_class_sizes,  # noqa: F401
                              check_no_singleton_class, ensemble_mean, nearest_same_class)
-from .methods import (CLUSTER_METHODS, COVARIANCE_METHODS, FEATURE_METHODS,  # noqa: F401
+from .methods import (CLUSTER_METHODS, COVARIANCE_METHODS, DENSITY_METHODS,  # noqa: F401
+                      FEATURE_METHODS,
                       FORWARD_FAMILY, FORWARD_SCORES, KNN_METHODS, LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS,
-                      SELECT_DIVERSITY, SELECT_FILLS, SELECT_POLICIES, check_diversity, check_fill,
+                      SELECT_DIVERSITY, SELECT_FILLS, SELECT_POLICIES, check_bandwidth,
+                      check_diversity, check_fill,
                       check_objective, check_selection, check_shrink, known, pass_of, refinable,
                       seed_counts)
 from .resnet import ResNet
@@ -81,6 +83,10 @@ class ScoreConfig:
     # shrinkage of "maha"'s covariance towards its mean eigenvalue, in [0, 1]: Sigma = S / N +
     # maha_shrink (trace(S / N) / D) I (0 needs more rows than N - C > D for a Cholesky factor)
     maha_shrink: float = 0.01
+    # bandwidth of the DENSITY_METHODS ("kde", "kde_post": the negative log kernel density among
+    # all feature rows and the negative log Parzen posterior of the own label): the weights are
+    # exp(-d^2 / (kde_bandwidth s)), s the mean squared distance between distinct rows; finite, > 0
+    kde_bandwidth: float = 0.25
     batch_size: int = 128                    # EL2N batch partition (config.yaml:7 batch_size)
     el2n_bn: str = "batch"                   # "batch" = reference semantics; "running" = eval
     grand_batch: int = 1024                  # GraNd chunk (eval BN: any size, same result)
@@ -200,6 +206,8 @@ class ScoreConfig:
                     raise ValueError(f"{name} must be an integer in {lo}..{hi} (got {v!r})")
         if any(m in COVARIANCE_METHODS for m in self.methods):
             self.maha_shrink = check_shrink(self.maha_shrink)
+        if any(m in DENSITY_METHODS for m in self.methods):
+            self.kde_bandwidth = check_bandwidth(self.kde_bandwidth)
         if self.el2n_bn not in ("batch", "running"):
             raise ValueError("el2n_bn must be 'batch' or 'running'")
         if self.pegrad_method not in _capi.METHODS:

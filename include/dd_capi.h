@@ -833,6 +833,48 @@ int dd_knn(const float* q, const int64_t* q_id, const int64_t* q_label, int64_t 
            void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------- *
+ * The kernel density of a row among ALL candidate rows in feature space (the soft form of
+ * dd_knn's scores: every other row votes, with a weight that decays with its distance), and the
+ * Parzen-window posterior of the row's own label.  Purely additive: dd_abi_version() stays 10.
+ *
+ *   w(r, j) = exp(-d^2(r, j) inv)         over the candidates j with c_id[j] != q_id[r]
+ *   nll[r]  = -ln sum_j w(r, j)
+ *   post[r] = ln sum_j w(r, j) - ln sum_{j : c_label[j] == q_label[r]} w(r, j)
+ *
+ * q, q_id, q_label, c, c_id, c_label and `operands` as for dd_knn (the labels may be NULL when
+ * neither post nor accum_post is asked for); inv = 1 / (bandwidth x scale) > 0, finite, a host
+ * float.  d^2 = max(0, key + ||q||^2) with dd_knn's key on split MFMA and both norms summed in
+ * fp32 in one order fixed by D; a d^2 below 2^-11 ||q||^2 (the key's own rounding) is taken again
+ * from the fp32 rows, sum_d (q[d] - c[d])^2 in one ascending fmaf chain, so an exact duplicate
+ * has weight exactly 1.  A candidate with a non-finite element (or whose key is not finite) adds
+ * nothing; a query with a non-finite element: NaN.  No candidate at all: nll = +inf; none with
+ * the query's label: post = +inf.  accum_nll[r] += nll[r], accum_post[r] += post[r].
+ *
+ * The sums are streaming log-sum-exps in base 2 (m, sigma: sum = sigma 2^m, rescaled when the
+ * running maximum rises), so a row whose every weight underflows fp32 still gets its exact log
+ * density.  A workgroup folds one segment of seg_rows candidates (a multiple of 128; 0 =
+ * 128 max(4, ceil(nc / 2048)), a function of nc alone; at most 64 segments) for 128 queries; a
+ * second kernel merges the segments in ascending order.  No atomics.
+ *
+ * Invariance: every output of row r depends on row r, on the candidates in their order, on D,
+ * inv and seg_rows: bitwise independent of nq, of the batching and the positions of the queries,
+ * of the buffers' alignment and of the launch geometry.
+ *
+ * Limits and errors as for dd_knn (DD_EINVAL with a message before any launch; nq == 0 returns
+ * DD_OK).  The workspace (dd_kde_workspace_bytes: host only, 0 for bad arguments) holds dd_knn's
+ * halves and candidate norms, 4 nq bytes of query norms and 16 nq segments bytes of partial
+ * sums.  No allocation, no synchronisation inside (graph-capturable); plain vector stores only.
+ * ---------------------------------------------------------------------------------------- */
+size_t dd_kde_workspace_bytes(int64_t nq, int64_t nc, int32_t D, int64_t seg_rows,
+                              int32_t operands);
+
+int dd_kde(const float* q, const int64_t* q_id, const int64_t* q_label, int64_t nq,
+           const float* c, const int64_t* c_id, const int64_t* c_label, int64_t nc, int32_t D,
+           float inv, int64_t seg_rows, int32_t operands, float* nll, float* post,
+           float* accum_nll, float* accum_post, void* workspace, size_t workspace_bytes,
+           void* stream);
+
+/* ---------------------------------------------------------------------------------------- *
  * Greedy k-center (farthest-first traversal; Sener & Savarese's core-set baseline) over feature
  * rows, inside groups: the coverage keep-set.  Purely additive: dd_abi_version() stays 10.
  *
