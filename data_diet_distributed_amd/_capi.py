@@ -53,6 +53,7 @@ EXPORTS = (
     "dd_kde_workspace_bytes", "dd_kde",
     "dd_kcenter_workspace_bytes", "dd_kcenter_seed_batch", "dd_kcenter_greedy",
     "dd_kmedoids_workspace_bytes", "dd_kmedoids_greedy",
+    "dd_herding_workspace_bytes", "dd_herding_greedy",
     "dd_d2_weights", "dd_d2_propagate", "dd_d2_workspace_bytes", "dd_d2_select",
     "dd_kmeans_workspace_bytes", "dd_kmeans_assign", "dd_kmeans_centroids",
     "dd_maha_workspace_bytes", "dd_maha_segment_rows", "dd_maha_scatter", "dd_maha_dist",
@@ -123,6 +124,9 @@ def lib():
                 "dd_kmedoids_workspace_bytes": (SZ, [I64, I32, I32, P, I64, I32]),
                 "dd_kmedoids_greedy": (I32, [P, P, I64, I32, P, P, I32, P, P, I64, P, I64, I32,
                                              I32, I32, P, P, P, P, P, SZ, P]),
+                "dd_herding_workspace_bytes": (SZ, [I64, I32, I32, P, I64, I32]),
+                "dd_herding_greedy": (I32, [P, P, I64, I32, P, P, I32, P, P, I64, P, I64, I32,
+                                            I32, P, P, P, P, SZ, P]),
                 "dd_d2_weights": (I32, [P, P, I64, I32, F32, P, P]),
                 "dd_d2_propagate": (I32, [P, P, P, I64, I32, P, P, P]),
                 "dd_d2_workspace_bytes": (SZ, [I64, I32]),
@@ -935,6 +939,72 @@ def kmedoids_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor,
     if check:
         check_kcenter(stat.tolist())
     return picked, gain, cur, stat
+
+
+def herding_workspace_bytes(n: int, D: int, sizes, steps: int, operands: str = "f16x3") -> int:
+    """Bytes of herding_greedy's workspace (dd_herding_workspace_bytes; 0 for sizes outside the
+    entry point's limits: a group above KMEDOIDS_MAX_GROUP_ROWS among them)."""
+    sizes = [int(v) for v in sizes]
+    return int(lib().dd_herding_workspace_bytes(int(n), int(D), len(sizes),
+                                                (ctypes.c_int64 * len(sizes))(*sizes),
+                                                int(steps), OPERANDS.get(operands, -1)))
+
+
+def herding_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor, seed_counts,
+                   picks, *, operands: str = "f16x3", blocks: int = 0, check: bool = True):
+    """Kernel herding inside groups (dd_herding_greedy): every pick is the unkept row that brings
+    the mean of the kept rows closest to the group's mean, the row with the largest
+    A_i - (t + 1) P_i (A_i: the sum of squared distances from the t kept rows to row i, P_i:
+    row i's squared distance to the group mean), a tie to the smaller id.  The arguments, the
+    sorting, the host rejections, `operands`, the group limit and `stat` are kmedoids_greedy's
+    (stat[0] also counts the rows with an element of magnitude >= 2^15, which the exact
+    fixed-point mean cannot hold).  Each group's whole loop runs in one persistent workgroup of
+    one launch.
+
+    Returns (picked int64 [steps, G], value fp32 [steps, G], None, stat int32 [2]): picked[t, g]
+    is the id group g takes at step t and value[t, g] its A - (t + 1) P (both -1 for
+    t >= picks[g]); the third entry stands where the other fills return a per-row distance.
+    `blocks`: workgroups per group of the mean's launch (0: chosen by the library); no output
+    depends on it."""
+    what = "herding_greedy"
+    n, D, G, sizes, seed_counts, picks, _, blocks = _greedy_check(
+        what, rows, sizes, seeds, seed_counts, picks, groups, 0, blocks)
+    if operands not in ("f16x3", "bf16x3"):
+        raise ValueError(f"{what}: operands must be 'f16x3' or 'bf16x3' (got {operands!r})")
+    if max(sizes) > KMEDOIDS_MAX_GROUP_ROWS:
+        raise ValueError(f"{what}: a group of {max(sizes)} rows is above the "
+                         f"{KMEDOIDS_MAX_GROUP_ROWS} whose distance matrix one call holds")
+    dev = rows.device
+    steps = max(picks)
+    sizes_h = (ctypes.c_int64 * G)(*sizes)
+    need = int(lib().dd_herding_workspace_bytes(n, D, G, sizes_h, steps, OPERANDS[operands]))
+    if need == 0:
+        raise ValueError(f"{what}: unsupported size n={n}, D={D}, G={G}")
+    stat = torch.zeros(2, dtype=torch.int32, device=dev)
+    picked = torch.full((steps, G), -1, dtype=torch.int64, device=dev)
+    value = torch.full((steps, G), -1.0, dtype=torch.float32, device=dev)
+    if n:
+        rows, ids, _, pos, off, seed_off, picks_d = _greedy_sort(
+            rows, ids, groups, G, sizes, seeds, seed_counts, picks, stat)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        e0 = _t0(rows, always=True)
+        rc = lib().dd_herding_greedy(
+            _dev(rows, torch.float32, "rows"), _dev(ids, torch.int64, "ids"), n, D,
+            _dev(off, torch.int64, "off"), sizes_h, G,
+            _opt(pos if pos.numel() else None, torch.int64, "seeds"),
+            _dev(seed_off, torch.int64, "seed_off"), max(seed_counts),
+            _dev(picks_d, torch.int64, "picks"), steps, OPERANDS[operands], blocks,
+            _opt(picked if steps else None, torch.int64, "picked"),
+            _opt(value if steps else None, torch.float32, "value"),
+            ctypes.c_void_p(stat.data_ptr()), _dev(ws, torch.uint8, "workspace"), need,
+            _stream(rows))
+        _check(rc, "dd_herding_greedy")
+        # the matrices written once, then one row of a group's per seed and pick
+        _t1(e0, "select", 4.0 * sum(s * s + s * (m + p)
+                                    for s, m, p in zip(sizes, seed_counts, picks)), rows)
+    if check:
+        check_kcenter(stat.tolist())
+    return picked, value, None, stat
 
 
 def check_kcenter(stat):

@@ -37,6 +37,7 @@ DEFAULTS = {
     "select_fill": "score",           # score (the rank cut) | kcenter (coverage: greedy k-center)
     "kcenter_seed_frac": 0.0,         # share of a quota seeded by the score (at least one seed)
     "kcenter_objective": "radius",    # radius (farthest-first) | inertia (greedy k-medoids)
+    "kcenter_match": "none",          # none | mean (kernel herding: the kept mean tracks the group's)
     "kcenter_ckpt": -1,               # the checkpoint whose feature rows the row-based
     #                                   selections read (the kcenter fill, the d2 diversity)
     "select_diversity": "none",       # none | d2 (D2 pruning: message passing on the kNN graph)

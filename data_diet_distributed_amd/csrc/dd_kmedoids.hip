@@ -6,19 +6,11 @@
 //                                sum_i cur_i the most and fold it in
 //
 // Launches on one stream, no allocation, no synchronisation, nothing read back:
-//   pack    feat::pack_kernel on the group-sorted rows: operand halves and ||f||^2 (NaN marks a
-//           non-finite row).
-//   layout  one workgroup: moff[g], the float offset of group g's matrix, from `off`.
+//   pack, layout, matrix  dd_distmat.h (shared with dd_herding.hip): the rows' operand halves and
+//           norms, moff[g], and once per call the groups' squared-distance matrices M, rows
+//           pitched to a multiple of 64 floats, the tail +0, the diagonal 0.  Only rows M[c][.]
+//           are ever read afterwards (by the seed fold, the pick fold and the gain alike).
 //   init    cur (both buffers and the caller's) = +inf, the slots = 0, the NaN norms counted.
-//   matrix  once per call.  Workgroup (x, g) takes 128 points of group g against a range of its
-//           centres, 128 at a time, through feat::scan_keys: THE key, so its invariance argument
-//           stays in dd_feat.h.  The scan leaves the POINT on the lane, so the epilogue stores
-//           M[c][.] with consecutive lanes on consecutive points: 128-byte runs per half wave.
-//           Rows are pitched to a multiple of 64 floats, the tail past n_g holds +0 and the
-//           diagonal is forced to 0.  Only rows M[c][.] are ever read afterwards (by the seed
-//           fold, the pick fold and the gain alike): one source of every distance, and the matrix
-//           need not be symmetric (it is not, bit for bit: the second and third split products
-//           swap with the operands).
 //   seed    launch j folds seeds [j S, (j + 1) S) of every group: cur_i = min(cur_i, M[s][i]), a
 //           seed's own entry -1 (kept).
 //   pick    launch t (t = 0 .. max picks): workgroup (b, g) leaves at once when t > picks[g].
@@ -40,23 +32,18 @@
 // add chain (kept rows and the tail add exact zeros: max(-1 - M, 0) = max(0 - 0, 0) = 0), then the
 // fixed butterfly.  The order depends on n_g alone, so a gain does not depend on the launch
 // geometry, the other groups or which wave computes it.
-#include "dd_feat.h"
+#include "dd_distmat.h"
 
 namespace dd {
 namespace kmedoids {
 
-using namespace feat;
+using namespace distmat;
 
 constexpr int kWaves = kThreads / kWave;
-constexpr int kMaxRows = DD_KMEDOIDS_MAX_GROUP_ROWS;
 constexpr int kMaxSeedBatch = DD_KCENTER_MAX_SEED_BATCH;
 constexpr int kMaxBlocks = DD_KCENTER_MAX_BLOCKS;
-constexpr int kMaxGroups = DD_KCENTER_MAX_GROUPS;
-constexpr int kTargetBlocks = 1024;  // workgroups of one launch the automatic count aims at
 constexpr int kCheckBlocks = 256;    // workgroups per group from which the slot is read first
 constexpr int kGainUnroll = 8;       // matrix loads a lane has in flight
-
-__host__ __device__ constexpr int64_t pitch_of(int64_t ng) { return (ng + 63) / 64 * 64; }
 
 // workgroups per group of the seed and pick launches (0: from the largest group and G alone)
 static int resolve_blocks(int64_t max_rows, int G, int blocks) {
@@ -67,89 +54,18 @@ static int resolve_blocks(int64_t max_rows, int G, int blocks) {
   return (int)b;
 }
 
-// the workspace: feat::PackLayout with no queries (the rows are points and centres at once: the
-// "candidate" halves and norms serve both), then the matrices' offsets, the matrices, the two cur
-// buffers and the slots
-struct Layout : PackLayout {
-  int64_t moff, mat, cur, slots, total;
-  int64_t max_rows;
+// the workspace: distmat::MatLayout (the halves, the norms, the matrices' offsets and the
+// matrices), then the two cur buffers and the slots
+struct Layout : MatLayout {
+  int64_t cur, slots, total;
 };
 static Layout layout(int64_t n, int D, int G, const int64_t* sizes, int64_t steps) {
   Layout L;
-  static_cast<PackLayout&>(L) = pack_layout(0, n, D);
-  int64_t floats = 0;
-  L.max_rows = 0;
-  for (int g = 0; g < G; ++g) {
-    floats += sizes[g] * pitch_of(sizes[g]);
-    if (sizes[g] > L.max_rows) L.max_rows = sizes[g];
-  }
-  L.moff = L.end;
-  L.mat = L.moff + align256(((int64_t)G + 1) * 8);
-  L.cur = L.mat + align256(floats * 4);
+  static_cast<MatLayout&>(L) = mat_layout(n, D, G, sizes);
+  L.cur = L.mat_end;
   L.slots = L.cur + align256(2 * n * 4);
   L.total = L.slots + align256((steps > 0 ? steps : 1) * (int64_t)G * 8);
   return L;
-}
-
-// `what` null: no error text (dd_kmedoids_workspace_bytes answers 0)
-static bool dims_ok(const char* what, int64_t n, int32_t D, int32_t G, const int64_t* sizes,
-                    int64_t steps, int32_t operands) {
-  if (!rows_dims_ok(what, 0, n, D, operands)) return false;
-  if (G < 1 || G > kMaxGroups || steps < 0 || steps > n || sizes == nullptr) {
-    if (what)
-      set_error("%s: need 1 <= G <= %d, 0 <= steps <= n and the groups' sizes (G=%d, "
-                "steps=%lld, n=%lld)", what, kMaxGroups, G, (long long)steps, (long long)n);
-    return false;
-  }
-  int64_t sum = 0;
-  for (int g = 0; g < G; ++g) {
-    if (sizes[g] < 0 || sizes[g] > kMaxRows) {
-      if (what)
-        set_error("%s: group %d has %lld rows; a group's distance matrix holds at most "
-                  "DD_KMEDOIDS_MAX_GROUP_ROWS = %d", what, g, (long long)sizes[g], kMaxRows);
-      return false;
-    }
-    sum += sizes[g];
-  }
-  if (sum > n) {
-    if (what)
-      set_error("%s: the groups' sizes sum to %lld, above n=%lld", what, (long long)sum,
-                (long long)n);
-    return false;
-  }
-  return true;
-}
-
-// moff[g] = sum over h < g of n_h pitch_h, g = 0 .. G (one workgroup; thread k sums a run of
-// consecutive groups, thread 0 scans the 256 partial sums)
-__global__ __launch_bounds__(kThreads) void layout_kernel(const int64_t* __restrict__ off, int G,
-                                                          int64_t* __restrict__ moff) {
-  __shared__ int64_t s_part[kThreads];
-  const int per = (G + kThreads - 1) / kThreads;
-  const int g0 = threadIdx.x * per, g1 = g0 + per < G ? g0 + per : G;
-  int64_t sum = 0;
-  for (int g = g0; g < g1; ++g) {
-    const int64_t ng = off[g + 1] - off[g];
-    sum += ng * pitch_of(ng);
-  }
-  s_part[threadIdx.x] = sum;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    int64_t run = 0;
-    for (int k = 0; k < kThreads; ++k) {
-      const int64_t v = s_part[k];
-      s_part[k] = run;
-      run += v;
-    }
-    moff[G] = run;
-  }
-  __syncthreads();
-  int64_t run = s_part[threadIdx.x];
-  for (int g = g0; g < g1; ++g) {
-    const int64_t ng = off[g + 1] - off[g];
-    moff[g] = run;
-    run += ng * pitch_of(ng);
-  }
 }
 
 __global__ __launch_bounds__(kThreads) void init_kernel(const float* __restrict__ norm, int64_t n,
@@ -165,49 +81,6 @@ __global__ __launch_bounds__(kThreads) void init_kernel(const float* __restrict_
   buf[n + i] = INFINITY;
   const float s = norm[i];
   if (s != s) atomicAdd(bad, 1);  // (pack_kernel's mark of a row with a NaN or an infinity)
-}
-
-// Workgroup (x, g): points [128 pt, 128 pt + 128) of group g against the centres of split sp,
-// x = pt csplit + sp (a split is a run of whole 128-centre steps).
-template <bool F16>
-__global__ __launch_bounds__(kThreads) void matrix_kernel(
-    const uint16_t* __restrict__ hi, const uint16_t* __restrict__ lo,
-    const float* __restrict__ norm, const int64_t* __restrict__ ids,
-    const int64_t* __restrict__ off, const int64_t* __restrict__ moff, int Dp, int csplit,
-    float* __restrict__ mat) {
-  __shared__ ScanLds lds;
-  const int g = blockIdx.y;
-  const int64_t r0 = off[g], r1 = off[g + 1];
-  const int ng = (int)(r1 - r0);
-  if (ng <= 0) return;  // (the whole workgroup, here and below)
-  float* __restrict__ M = mat + moff[g];
-  const int pitch = (int)pitch_of(ng);
-  if (ng == 1) {  // one row: its own distance and the tail
-    if (blockIdx.x == 0 && threadIdx.x < pitch) M[threadIdx.x] = 0.f;
-    return;
-  }
-  const int pt = blockIdx.x / csplit, sp = blockIdx.x % csplit;
-  if (pt * TQ >= ng) return;
-  const int ctiles = (ng + TC - 1) / TC;
-  const int64_t span = (int64_t)((ctiles + csplit - 1) / csplit) * TC;  // centres per split
-  const int64_t cs = r0 + sp * span, ce = cs + span < r1 ? cs + span : r1;
-  if (cs >= ce) return;
-
-  const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
-  const int li = pt * TQ + wave * 32 + (lane & 31);  // this lane's point (both lane halves hold it)
-  const int64_t qr = r0 + li;
-  const bool qvalid = li < ng;
-  const uint16_t* __restrict__ qh_row = hi + (qvalid ? qr : r0) * (int64_t)Dp;
-  const uint16_t* __restrict__ ql_row = lo + (qvalid ? qr : r0) * (int64_t)Dp;
-  const float fn = qvalid ? norm[qr] : 0.f;
-  const bool store = li < pitch;  // the tail [n_g, pitch) is written too: +0
-  scan_keys<F16>(lds, qh_row, ql_row, qvalid, hi, lo, norm, ids, cs, ce, Dp,
-                 [&](float key, int lr, int64_t c0) {
-                   const int64_t c = c0 + lr;
-                   if (!store || c >= ce) return;
-                   const float d2 = qvalid && c != qr ? fmaxf(fn + key, 0.f) : 0.f;
-                   M[(c - r0) * pitch + li] = d2;
-                 });
 }
 
 // Seed launch `batch`: workgroup (b, g) folds centres seeds[s0 + batch S .. + S) of group g, whose
@@ -377,24 +250,14 @@ struct Args {
 
 template <bool F16>
 static void launch(const Args& a, char* ws, const Layout& L, hipStream_t st) {
-  uint16_t *hi = at<uint16_t>(ws, L.c_hi), *lo = at<uint16_t>(ws, L.c_lo);
   float *norm = at<float>(ws, L.c_norm), *mat = at<float>(ws, L.mat), *buf = at<float>(ws, L.cur);
   int64_t* moff = at<int64_t>(ws, L.moff);
   unsigned long long* slots = at<unsigned long long>(ws, L.slots);
   const int64_t nslots = a.steps * a.G;
-  pack_kernel<F16><<<(unsigned)ceil_div(a.n, kRows), kThreads, 0, st>>>(a.rows, a.n, a.D, L.Dp, hi,
-                                                                        lo, norm, nullptr);
-  layout_kernel<<<1, kThreads, 0, st>>>(a.off, a.G, moff);
+  launch_matrices<F16>(a.rows, a.ids, a.off, a.n, a.D, a.G, ws, L, st);
   init_kernel<<<(unsigned)ceil_div(a.n > nslots ? a.n : nslots, kThreads), kThreads, 0, st>>>(
       norm, a.n, nslots, a.cur, buf, slots, a.bad);
   if (L.max_rows == 0) return;  // every group is empty
-  // the matrix: 128-point tiles of the largest group, the centres split until the launch has
-  // about kTargetBlocks workgroups (smaller groups leave at once where they have no tile)
-  const int tiles = (int)ceil_div(L.max_rows, TQ);
-  int csplit = (int)ceil_div(kTargetBlocks, (int64_t)tiles * a.G);
-  if (csplit > tiles) csplit = tiles;
-  matrix_kernel<F16><<<dim3((unsigned)(tiles * csplit), (unsigned)a.G), kThreads, 0, st>>>(
-      hi, lo, norm, a.ids, a.off, moff, L.Dp, csplit, mat);
   const dim3 grid((unsigned)a.blocks, (unsigned)a.G);
   for (int64_t j = 0; j * a.S < a.max_seeds; ++j)
     seed_kernel<<<grid, kThreads, 0, st>>>(mat, a.off, moff, a.seeds, a.seed_off, (int)j, a.S,

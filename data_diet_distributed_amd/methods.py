@@ -161,6 +161,30 @@ def check_objective(objective, name="kcenter_objective") -> str:
     return objective
 
 
+# Whether the centre-based fill ("kcenter") matches a moment of its group instead of covering it:
+#   "none"  the fill picks by kcenter_objective
+#   "mean"  kernel herding (Welling; DeepCore's Herding, iCaRL's exemplar rule): every pick is the
+#           row that brings the mean of the kept rows closest to the group's mean
+#           (dd_herding_greedy).  The seeds, the groups and the quotas are the fill's.
+KCENTER_MATCH = ("none", "mean")
+
+
+def check_match(match, fill="kcenter", objective="radius", *, name="kcenter_match",
+                fill_name="select_fill", objective_name="kcenter_objective") -> str:
+    """ScoreConfig's kcenter_match, and select_with_policy's / sparse_loader's `match` under their
+    own names: one of KCENTER_MATCH (checked whatever the fill); "mean" replaces the picks of the
+    kcenter fill, so it needs that fill and the default objective."""
+    if match not in KCENTER_MATCH:
+        raise ValueError(f"{name} must be one of {KCENTER_MATCH} (got {match!r})")
+    if match == "mean" and fill != "kcenter":
+        raise ValueError(f"{name}='mean' needs {fill_name}='kcenter' (got {fill!r}): herding "
+                         f"fills the quotas of the centre-based fill")
+    if match == "mean" and objective != "radius":
+        raise ValueError(f"{name}='mean' needs {objective_name}='radius', the default (got "
+                         f"{objective!r}): the picks follow one rule")
+    return match
+
+
 # Whether the rank cut (select_fill "score") also weighs coverage:
 #   "none"  the rank cut as it is
 #   "d2"    D2 pruning (Maharana, Yadav & Bansal): the examples sit on the d2_k-nearest-neighbour

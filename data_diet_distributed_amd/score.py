@@ -25,7 +25,8 @@ rest (config.DEFAULTS):
                      quotas over the pooled feature rows (--fill); kcenter_seed_frac: the share
                      of a quota seeded by the score; kcenter_ckpt: whose rows (default: the last);
                      kcenter_objective: radius (farthest-first) | inertia (greedy k-medoids,
-                     --fill-objective)
+                     --fill-objective); kcenter_match: none | mean (kernel herding: the kept rows'
+                     mean tracks the group's, --fill-match)
   select_diversity   none | d2: D2 pruning on the d2_k-nearest-neighbour graph of kcenter_ckpt's
                      feature rows (--diversity, --d2-k); d2_gamma_f / d2_gamma_r: the forward /
                      reverse edge weights' sharpness (--d2-gamma-f, --d2-gamma-r)
@@ -156,6 +157,7 @@ def engine_config(cfg):
                        kcenter_seed_frac=float(cfg.get("kcenter_seed_frac", 0.0)),
                        kcenter_ckpt=int(cfg.get("kcenter_ckpt", -1)),
                        kcenter_objective=cfg.get("kcenter_objective", "radius"),
+                       kcenter_match=cfg.get("kcenter_match", "none"),
                        select_diversity=cfg.get("select_diversity", "none"),
                        d2_k=cfg.get("d2_k", 10), d2_gamma_f=cfg.get("d2_gamma_f", 1.0),
                        d2_gamma_r=cfg.get("d2_gamma_r", 1.0),
@@ -222,7 +224,9 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
             meta.update(select_fill=sel["fill"], kcenter_seed_frac=ecfg.kcenter_seed_frac,
                         kcenter_ckpt=ecfg.kcenter_ckpt % K, select_policy=sel["policy"],
                         class_quota=sel["class_quota"], class_seeds=sel["class_seeds"],
-                        radius=json_radius(sel["radius"]))
+                        radius=None if sel["radius"] is None else json_radius(sel["radius"]))
+            if sel.get("match", "none") != "none":  # (the default: metadata unchanged)
+                meta.update(kcenter_match=sel["match"], mean_gap=sel["mean_gap"])
             if sel.get("objective", "radius") != "radius":  # (the default: metadata unchanged)
                 meta.update(kcenter_objective=sel["objective"],
                             inertia=json_radius(sel["inertia"]))
@@ -260,6 +264,9 @@ def parse(argv=None):
     ap.add_argument("--fill-objective", default=None, choices=("radius", "inertia"),
                     help="what the kcenter fill minimises (default: kcenter_objective of the "
                          "config)")
+    ap.add_argument("--fill-match", default=None, choices=("none", "mean"),
+                    help="whether the kcenter fill matches its group's mean instead (kernel "
+                         "herding; default: kcenter_match of the config)")
     ap.add_argument("--diversity", default=None, choices=("none", "d2"),
                     help="whether the score fill weighs coverage (default: select_diversity of "
                          "the config)")
@@ -280,6 +287,7 @@ def apply_overrides(cfg: dict, args) -> dict:
     place)."""
     for key, v in (("select_policy", args.policy), ("select_skip", args.skip),
                    ("select_fill", args.fill), ("kcenter_objective", args.fill_objective),
+                   ("kcenter_match", args.fill_match),
                    ("select_diversity", args.diversity), ("d2_k", args.d2_k),
                    ("d2_gamma_f", args.d2_gamma_f), ("d2_gamma_r", args.d2_gamma_r),
                    ("kde_bandwidth", args.kde_bandwidth)):

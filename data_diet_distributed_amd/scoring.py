@@ -53,7 +53,7 @@ from .methods import (CLUSTER_METHODS, COVARIANCE_METHODS, DENSITY_METHODS,  # n
                       FORWARD_FAMILY, FORWARD_SCORES, KNN_METHODS, LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS,
                       SELECT_DIVERSITY, SELECT_FILLS, SELECT_POLICIES, check_bandwidth,
                       check_diversity, check_fill,
-                      check_objective, check_selection, check_shrink, known, pass_of, refinable,
+                      check_match, check_objective, check_selection, check_shrink, known, pass_of, refinable,
                       seed_counts)
 from .resnet import ResNet
 
@@ -170,10 +170,17 @@ class ScoreConfig:
     # dd_kmedoids_greedy: representative rows where "radius" takes the outliers; a group holds at
     # most _capi.KMEDOIDS_MAX_GROUP_ROWS rows), and last_selection also records each group's
     # inertia.  It is validated whatever the fill, like kcenter_seed_frac.
+    # kcenter_match (methods.KCENTER_MATCH): "mean" keeps the fill's groups, quotas and seeds and
+    # picks by kernel herding instead: each pick is the row that brings the mean of the group's
+    # kept rows closest to the group's mean (dd_herding_greedy, a group's whole loop in one
+    # persistent workgroup; groups of at most _capi.KMEDOIDS_MAX_GROUP_ROWS rows).  It needs
+    # select_fill = "kcenter" and the default objective; last_selection records each group's
+    # mean_gap = || mean(group) - mean(kept) ||_2 and no radius.
     select_fill: str = "score"
     kcenter_seed_frac: float = 0.0
     kcenter_ckpt: int = -1
     kcenter_objective: str = "radius"
+    kcenter_match: str = "none"
     # Whether the score fill also weighs coverage (methods.SELECT_DIVERSITY): "d2" is D2 pruning:
     # on the d2_k-nearest-neighbour graph of checkpoint kcenter_ckpt's feature rows a score first
     # absorbs its neighbours' (edge weights exp(-d2_gamma_f d^2 / mean d^2)), then the quotas of
@@ -232,6 +239,7 @@ class ScoreConfig:
                                            seed_frac=self.kcenter_seed_frac)
         self.kcenter_seed_frac = float(self.kcenter_seed_frac)
         check_objective(self.kcenter_objective)
+        check_match(self.kcenter_match, self.select_fill, self.kcenter_objective)
         if isinstance(self.kcenter_ckpt, bool) or not isinstance(self.kcenter_ckpt,
                                                                  (int, np.integer)):
             raise ValueError(f"kcenter_ckpt must be an integer (got {self.kcenter_ckpt!r})")
@@ -309,7 +317,7 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
                        skip: int = 0, check_nan: bool = True, fill: str = "score",
                        seed_frac: float = 0.0, rows: Optional[torch.Tensor] = None,
                        objective: str = "radius", diversity: str = "none", d2_k: int = 10,
-                       gamma_f: float = 1.0, gamma_r: float = 1.0):
+                       gamma_f: float = 1.0, gamma_r: float = 1.0, match: str = "none"):
     """The keep-set of `k` of the n = keys.numel() examples under a selection policy
     (ScoreConfig.select_policy / select_skip), in dd_select_topk's order: key descending, ties
     by ascending index.  `labels` (int64 [n], on the keys' device) and `num_classes` are read
@@ -340,6 +348,13 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     the same one read.  A group holds at most _capi.KMEDOIDS_MAX_GROUP_ROWS rows, so "global"
     serves small sets only: a larger one raises and names the class policies.
 
+    match="mean" (ScoreConfig.kcenter_match; needs fill = "kcenter" and objective = "radius"):
+    dd_herding_greedy makes the picks instead, each the row that brings the mean of the group's
+    kept rows closest to the group's mean.  The seeds and the order of `kept` are as above; the
+    record gets "match" and "mean_gap", per group || mean(group) - mean(kept rows) ||_2 in float64
+    from the rows (None for a group that keeps nothing), and its "radius" stays None.  The group
+    limit and its error under "global" are objective="inertia"'s.
+
     diversity="d2" (ScoreConfig.select_diversity; needs fill = "score", skip = 0 and `rows`): D2
     pruning.  The groups and quotas are the policy's ("global": one group with quota k).  dd_knn
     gives every row its d2_k nearest other rows of `rows` (nbr_id, dist); scale = the float64 mean
@@ -358,6 +373,8 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     seed_frac = check_fill(fill, seed_frac, skip, fill_name="fill", frac_name="seed_frac",
                            skip_name="skip")
     check_objective(objective, "objective")
+    check_match(match, fill, objective, name="match", fill_name="fill",
+                objective_name="objective")
     d2_k, gamma_f, gamma_r = check_diversity(
         diversity, d2_k, gamma_f, gamma_r, fill, skip, name="diversity", k_name="d2_k",
         gamma_f_name="gamma_f", gamma_r_name="gamma_r", fill_name="fill", skip_name="skip")
@@ -376,18 +393,21 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
         rec.update(fill=fill, class_seeds=None, radius=None)
         if objective != "radius":
             rec.update(objective=objective, inertia=None)
+        if match != "none":
+            rec.update(match=match, mean_gap=None)
         if rows is None or rows.dim() != 2 or rows.shape[0] != n:
             raise ValueError(f"fill='kcenter' needs rows [n = {n}, D] (got "
                              f"{None if rows is None else tuple(rows.shape)})")
     if policy == "global":
         if fill == "kcenter":
-            if objective == "inertia" and n > _capi.KMEDOIDS_MAX_GROUP_ROWS:
-                raise ValueError(f"objective='inertia' under policy='global' holds one n x n "
+            if (objective == "inertia" or match == "mean") and n > _capi.KMEDOIDS_MAX_GROUP_ROWS:
+                what = "objective='inertia'" if objective == "inertia" else "match='mean'"
+                raise ValueError(f"{what} under policy='global' holds one n x n "
                                  f"distance matrix: n = {n} is above "
                                  f"{_capi.KMEDOIDS_MAX_GROUP_ROWS}; use a class policy "
                                  f"('stratified' or 'balanced'), whose groups are the classes")
             return _kcenter_fill(keys, None, [n], [k], rows.contiguous(), seed_frac, rec,
-                                 check_nan, objective)
+                                 check_nan, objective, match)
         if d2:
             return _d2_fill(keys, None, [k], rows.contiguous(), d2_k, gamma_f, gamma_r, rec,
                             check_nan)
@@ -405,7 +425,7 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     rec.update(class_counts=n_c, class_skip=s, class_quota=q)
     if fill == "kcenter":
         return _kcenter_fill(keys, labels, n_c, q, rows.contiguous(), seed_frac, rec, check_nan,
-                             objective)
+                             objective, match)
     if d2:
         if C > _capi.D2_MAX_GROUPS:
             raise ValueError(f"diversity='d2' holds at most {_capi.D2_MAX_GROUPS} groups "
@@ -452,9 +472,10 @@ def _d2_fill(keys, labels, quotas, rows, d2_k, gamma_f, gamma_r, rec, check_nan)
 
 
 def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan,
-                  objective="radius"):
+                  objective="radius", match="none"):
     """select_with_policy's kcenter fill over the groups `labels` (None: one group) of `sizes`
-    members with `quotas`, the picks by `objective`; completes and returns (kept, rec)."""
+    members with `quotas`, the picks by `objective` (by herding with match="mean"); completes and
+    returns (kept, rec)."""
     G, dev = len(sizes), keys.device
     m = seed_counts(quotas, seed_frac)
     if labels is None:
@@ -463,13 +484,19 @@ def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan,
         seeds, nan, _ = _capi.select_topk_by_class(keys, labels, G, [0] * G, m, k_total=sum(m),
                                                    check=False)
     picks = [q - a for q, a in zip(quotas, m)]
-    greedy = _capi.kmedoids_greedy if objective == "inertia" else _capi.kcenter_greedy
+    if match == "mean":
+        greedy = _capi.herding_greedy
+    else:
+        greedy = _capi.kmedoids_greedy if objective == "inertia" else _capi.kcenter_greedy
     picked, _, mind2, stat = greedy(rows, None, labels, sizes, seeds, m, picks, check=False)
     # by (step, group): the (t, g) with t < picks[g], their positions built on the host (a
     # boolean mask would make the host wait for the size of its result)
     p = np.asarray(picks, dtype=np.int64)
     live = np.flatnonzero(np.arange(picked.shape[0], dtype=np.int64)[:, None] < p[None, :])
     kept = torch.cat([seeds, picked.flatten().index_select(0, torch.from_numpy(live).to(dev))])
+    if match == "mean":
+        return kept, _mean_gap_record(rows, labels, sizes, quotas, kept, m, nan, stat, rec,
+                                      check_nan)
     # the covering radius per group: the largest squared distance left (kept rows hold -1)
     far = torch.zeros(G, dtype=torch.float32, device=dev)
     grp = labels if labels is not None else torch.zeros(keys.numel(), dtype=torch.int64,
@@ -490,6 +517,30 @@ def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan,
     if objective == "inertia":
         rec.update(inertia=[float(v) for v in host[3 + G:]])
     return kept, rec
+
+
+def _mean_gap_record(rows, labels, sizes, quotas, kept, m, nan, stat, rec, check_nan):
+    """The record of a herding fill: per group || mean(group) - mean(kept rows) ||_2 in float64
+    from the rows, and the one read after the loop (the keys' NaN count, the rows' and ids'
+    counts, the gaps)."""
+    G, dev = len(sizes), rows.device
+    grp = labels if labels is not None else torch.zeros(rows.shape[0], dtype=torch.int64,
+                                                        device=dev)
+    r64 = rows.to(torch.float64)
+
+    def means(idx, counts):
+        s = torch.zeros((G, rows.shape[1]), dtype=torch.float64, device=dev)
+        s.index_add_(0, grp[idx], r64[idx])
+        return s / torch.tensor(counts, dtype=torch.float64, device=dev).clamp(min=1)[:, None]
+
+    gap = (means(torch.arange(rows.shape[0], device=dev), sizes) - means(kept, quotas)).norm(dim=1)
+    host = torch.cat([nan.to(torch.float64), stat.to(torch.float64), gap]).tolist()
+    if check_nan and host[0]:
+        raise ValueError(f"{int(host[0])} NaN score(s): the keep-set is undefined")
+    _capi.check_kcenter(host[1:3])
+    rec.update(class_seeds=m, mean_gap=[float(v) if q else None
+                                        for v, q in zip(host[3:], quotas)])
+    return rec
 
 
 def normalize_refine(v) -> Union[bool, str]:
@@ -1146,7 +1197,8 @@ class ScoringEngine:
             kept, self.last_selection = select_with_policy(
                 keys, all_labels, self.models[0].linear.out_features, k, c.select_policy,
                 c.select_skip, check_nan, fill=c.select_fill, seed_frac=c.kcenter_seed_frac,
-                objective=c.kcenter_objective, diversity=c.select_diversity, d2_k=c.d2_k,
+                objective=c.kcenter_objective, match=c.kcenter_match,
+                diversity=c.select_diversity, d2_k=c.d2_k,
                 gamma_f=c.d2_gamma_f, gamma_r=c.d2_gamma_r,
                 rows=self._kcenter_rows if c.row_selection() is not None else None)
             return kept

@@ -1006,6 +1006,64 @@ int dd_kmedoids_greedy(const float* rows, const int64_t* ids, int64_t n, int32_t
                        size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------- *
+ * Kernel herding (Welling, "Herding dynamical weights to learn"; the Herding selector of
+ * DeepCore, iCaRL's exemplar rule) over feature rows, inside groups: the keep-set whose mean
+ * tracks its group's mean.  Purely additive: dd_abi_version() stays 10.
+ *
+ * rows, ids, off, sizes, seeds, seed_off, max_seeds, picks, steps and operands are
+ * dd_kmedoids_greedy's, and M is ITS matrix, bit for bit (one builder, shared).  Inside one group
+ * of n_g rows, with S the kept rows and t = |S|:
+ *
+ *   mu        = the group's mean: mu[d] = (float)(((double)sum_i q(f_i[d]) / n_g) * 2^-24), the
+ *               sum in int64 with q(v) = round-to-nearest-even(v * 2^24) as in
+ *               dd_class_feature_sums, so it does not depend on the order of the rows.
+ *   P_i       = sum_d (f_i[d] - mu[d])^2 in fp32 from the fp32 rows, dd_proto_scores' reduction
+ *               (lane l takes columns l, l + 64, ... in one fmaf chain, then a fixed butterfly).
+ *   A_i       = sum over s in S of M[s][i], one fp32 add chain: the seeds in ascending position
+ *               (a seed outside its group is ignored), then the picks in pick order.
+ *   step t of group g (t < picks[g]; `t` below counts the seeds too): the unkept row with the
+ *               largest v_i = fma(-(t + 1), P_i, A_i) is taken, a tie to the smaller id.  That is
+ *               the row minimising || (t + 1) mu - sum_{s in S} f_s - f_i ||^2: the one that
+ *               brings the mean of the kept rows closest to mu.
+ *               picked[t][g] = its id,  value[t][g] = its v,  then A_i += M[pick][i].
+ *   and (t, g) with t >= picks[g]: picked = -1, value = -1.  On small-integer rows whose mean is
+ *   a dyadic fraction every quantity is exact.
+ *   bad[0] += the rows of the groups with an element that is NaN, infinite or has |v| >= 2^15
+ *   (the fixed point's range).  Such a row adds nothing to the sums and is never picked; the
+ *   caller clears bad and rejects the call's results when it is non-zero.  A group whose every
+ *   unkept row is such a row ends its picks early (the rest stay -1).
+ *
+ * Launches (all on `stream`, nothing read back, no allocation): the pack and the matrices as in
+ * dd_kmedoids_greedy; one init; the sums (`blocks` workgroups per group, 0: from the largest
+ * group and G alone; integer atomics, so no output depends on it), the means and P; then ONE
+ * select launch of G workgroups of 1024 threads.  Workgroup g runs group g's whole loop: a thread
+ * keeps A and P of its rows (up to 16) in registers, a fold reads one row M[j][.], a pick is a
+ * maximum over (ordered(v) << 32) | ~position through a wave butterfly and sixteen LDS entries
+ * with one workgroup barrier; ordered() maps floats, negative ones too, onto unsigned integers in
+ * their order.  No launch per pick, and no kernel waits for another workgroup.
+ *
+ * Invariance: M, mu and P are functions of the group's rows (M, P: in id order; mu: as a set) and
+ * D alone, and A_i is summed in pick order, which the group's contents fix; so every output is
+ * bitwise independent of blocks, the rows' placement, the other groups and their layout.
+ *
+ * Limits: dd_kmedoids_greedy's (0 <= sizes[g] <= DD_KMEDOIDS_MAX_GROUP_ROWS; no seed_batch).
+ * Outside them, a NULL buffer the call would touch or a workspace below
+ * dd_herding_workspace_bytes or not 16-byte aligned is DD_EINVAL with a message before any
+ * launch.  n == 0 returns DD_OK.  The workspace (host only; 0 for bad arguments) holds the halves,
+ * norms, offsets and matrices of dd_kmedoids_greedy's, then 12 G D bytes of sums and means and
+ * 4 n bytes of P, each region rounded up to 256.
+ * ---------------------------------------------------------------------------------------- */
+size_t dd_herding_workspace_bytes(int64_t n, int32_t D, int32_t G, const int64_t* sizes,
+                                  int64_t steps, int32_t operands);
+
+int dd_herding_greedy(const float* rows, const int64_t* ids, int64_t n, int32_t D,
+                      const int64_t* off, const int64_t* sizes, int32_t G, const int64_t* seeds,
+                      const int64_t* seed_off, int64_t max_seeds, const int64_t* picks,
+                      int64_t steps, int32_t operands, int32_t blocks, int64_t* picked,
+                      float* value, int32_t* bad, void* workspace, size_t workspace_bytes,
+                      void* stream);
+
+/* ---------------------------------------------------------------------------------------- *
  * D2 pruning (Maharana, Yadav & Bansal, "D2 Pruning: Message Passing for Balancing Diversity and
  * Difficulty in Data Pruning") on a k-nearest-neighbour graph: the keep-set that weighs difficulty
  * against coverage.  Purely additive: dd_abi_version() stays 10.
