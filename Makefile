@@ -31,8 +31,9 @@ all: $(LIB)
 # dd_kde.hip too: its sums of sixteen exponentials per block and the fmaf chain that measures a
 # near-duplicate pair again each have one order, on which its bitwise claims rest.
 # dd_herding.hip too: every A_i is one fp32 add chain in pick order, on which its bitwise claim rests.
+# dd_cover.hip too: it compiles the same P_i (dd_groupmean.h) and must get herding's values.
 # The older units keep the flags their recorded results and timings were taken with.
-$(OBJDIR)/dd_kmeans.o $(OBJDIR)/dd_kmedoids.o $(OBJDIR)/dd_maha.o $(OBJDIR)/dd_d2.o $(OBJDIR)/dd_kde.o $(OBJDIR)/dd_herding.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
+$(OBJDIR)/dd_kmeans.o $(OBJDIR)/dd_kmedoids.o $(OBJDIR)/dd_maha.o $(OBJDIR)/dd_d2.o $(OBJDIR)/dd_kde.o $(OBJDIR)/dd_herding.o $(OBJDIR)/dd_cover.o: HIPFLAGS += -Xclang -target-feature -Xclang -packed-fp32-ops
 
 $(OBJDIR)/%.o: data_diet_distributed_amd/csrc/%.hip $(HDR)
 	@mkdir -p $(OBJDIR)

@@ -54,6 +54,7 @@ EXPORTS = (
     "dd_kcenter_workspace_bytes", "dd_kcenter_seed_batch", "dd_kcenter_greedy",
     "dd_kmedoids_workspace_bytes", "dd_kmedoids_greedy",
     "dd_herding_workspace_bytes", "dd_herding_greedy",
+    "dd_cover_workspace_bytes", "dd_cover_greedy",
     "dd_d2_weights", "dd_d2_propagate", "dd_d2_workspace_bytes", "dd_d2_select",
     "dd_kmeans_workspace_bytes", "dd_kmeans_assign", "dd_kmeans_centroids",
     "dd_maha_workspace_bytes", "dd_maha_segment_rows", "dd_maha_scatter", "dd_maha_dist",
@@ -127,6 +128,9 @@ def lib():
                 "dd_herding_workspace_bytes": (SZ, [I64, I32, I32, P, I64, I32]),
                 "dd_herding_greedy": (I32, [P, P, I64, I32, P, P, I32, P, P, I64, P, I64, I32,
                                             I32, P, P, P, P, SZ, P]),
+                "dd_cover_workspace_bytes": (SZ, [I64, I32, I32, P, I64, I32]),
+                "dd_cover_greedy": (I32, [P, P, I64, I32, P, P, I32, P, P, I64, P, I64, I32, I32,
+                                          F64, P, P, P, P, P, P, P, SZ, P]),
                 "dd_d2_weights": (I32, [P, P, I64, I32, F32, P, P]),
                 "dd_d2_propagate": (I32, [P, P, P, I64, I32, P, P, P]),
                 "dd_d2_workspace_bytes": (SZ, [I64, I32]),
@@ -744,8 +748,10 @@ def kcenter_workspace_bytes(n: int, D: int, G: int, steps: int) -> int:
     return int(lib().dd_kcenter_workspace_bytes(int(n), int(D), int(G), int(steps)))
 
 
-def _greedy_check(what, rows, sizes, seeds, seed_counts, picks, groups, seed_batch, blocks):
-    """The host rejections kcenter_greedy and kmedoids_greedy share, under the caller's name.
+def _greedy_check(what, rows, sizes, seeds, seed_counts, picks, groups, seed_batch, blocks,
+                  seedless=False):
+    """The host rejections kcenter_greedy and kmedoids_greedy share, under the caller's name
+    (seedless: a group may pick without a seed).
     Returns (n, D, G, sizes, seed_counts, picks, seed_batch, blocks) as host ints."""
     _dev(rows, torch.float32, "rows", 2)
     n, D = rows.shape
@@ -761,7 +767,7 @@ def _greedy_check(what, rows, sizes, seeds, seed_counts, picks, groups, seed_bat
         if seed_counts[g] + picks[g] > sizes[g]:
             raise ValueError(f"{what}: group {g} of {sizes[g]} rows cannot keep "
                              f"{seed_counts[g]} seeds + {picks[g]} picks")
-        if picks[g] and not seed_counts[g]:
+        if picks[g] and not seed_counts[g] and not seedless:
             raise ValueError(f"{what}: group {g} has picks but no seed")
     _dev(seeds, torch.int64, "seeds", 1)
     if seeds.numel() != sum(seed_counts):
@@ -1005,6 +1011,84 @@ def herding_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor, 
     if check:
         check_kcenter(stat.tolist())
     return picked, value, None, stat
+
+
+def cover_workspace_bytes(n: int, D: int, sizes, steps: int, operands: str = "f16x3") -> int:
+    """Bytes of cover_greedy's workspace (dd_cover_workspace_bytes; 0 for sizes outside the entry
+    point's limits: a group above KMEDOIDS_MAX_GROUP_ROWS among them)."""
+    sizes = [int(v) for v in sizes]
+    return int(lib().dd_cover_workspace_bytes(int(n), int(D), len(sizes),
+                                              (ctypes.c_int64 * len(sizes))(*sizes),
+                                              int(steps), OPERANDS.get(operands, -1)))
+
+
+def cover_greedy(rows: torch.Tensor, ids, groups, sizes, seeds: torch.Tensor, seed_counts, picks,
+                 prio: torch.Tensor, cover_radius: float, *, operands: str = "f16x3",
+                 blocks: int = 0, check: bool = True):
+    """Greedy maximum coverage inside groups (dd_cover_greedy): with theta = cover_radius times
+    the group's mean squared pairwise distance, every pick is the unkept row whose theta-ball
+    holds the most rows that are not yet within theta of a kept row, a tie to the smaller `prio`
+    (int32 [n] in the order of `rows`, unique within a group, in [0, group size)).  The other
+    arguments, the sorting, the host rejections, `operands`, the group limit and `stat` are
+    herding_greedy's, but a group may pick without a seed.  The squared-distance matrix is
+    thresholded into bits once, and each group's whole loop runs in one persistent workgroup of
+    one launch.
+
+    Returns (picked int64 [steps, G], gain int32 [steps, G], (theta fp32 [G], covered int64 [G]),
+    stat int32 [2]): picked[t, g] is the id group g takes at step t and gain[t, g] the rows it
+    newly covers (both -1 for t >= picks[g]); covered[g] counts the rows within theta[g] of a kept
+    row at the end.  `blocks`: workgroups per group of the mean's launch (0: chosen by the
+    library); no output depends on it."""
+    what = "cover_greedy"
+    n, D, G, sizes, seed_counts, picks, _, blocks = _greedy_check(
+        what, rows, sizes, seeds, seed_counts, picks, groups, 0, blocks, seedless=True)
+    if operands not in ("f16x3", "bf16x3"):
+        raise ValueError(f"{what}: operands must be 'f16x3' or 'bf16x3' (got {operands!r})")
+    if max(sizes) > KMEDOIDS_MAX_GROUP_ROWS:
+        raise ValueError(f"{what}: a group of {max(sizes)} rows is above the "
+                         f"{KMEDOIDS_MAX_GROUP_ROWS} whose distance matrix one call holds")
+    cover_radius = float(cover_radius)
+    if not 0.0 < cover_radius < float("inf"):
+        raise ValueError(f"{what}: cover_radius must be finite and > 0 (got {cover_radius!r})")
+    _dev(prio, torch.int32, "prio", 1)
+    if prio.numel() != n:
+        raise ValueError("prio must have one entry per row")
+    dev = rows.device
+    steps = max(picks)
+    sizes_h = (ctypes.c_int64 * G)(*sizes)
+    need = int(lib().dd_cover_workspace_bytes(n, D, G, sizes_h, steps, OPERANDS[operands]))
+    if need == 0:
+        raise ValueError(f"{what}: unsupported size n={n}, D={D}, G={G}")
+    stat = torch.zeros(2, dtype=torch.int32, device=dev)
+    picked = torch.full((steps, G), -1, dtype=torch.int64, device=dev)
+    gain = torch.full((steps, G), -1, dtype=torch.int32, device=dev)
+    theta = torch.zeros(G, dtype=torch.float32, device=dev)
+    covered = torch.zeros(G, dtype=torch.int64, device=dev)
+    if n:
+        rows, ids, order, pos, off, seed_off, picks_d = _greedy_sort(
+            rows, ids, groups, G, sizes, seeds, seed_counts, picks, stat)
+        if order is not None:
+            prio = prio.index_select(0, order)
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        e0 = _t0(rows, always=True)
+        rc = lib().dd_cover_greedy(
+            _dev(rows, torch.float32, "rows"), _dev(ids, torch.int64, "ids"), n, D,
+            _dev(off, torch.int64, "off"), sizes_h, G,
+            _opt(pos if pos.numel() else None, torch.int64, "seeds"),
+            _dev(seed_off, torch.int64, "seed_off"), max(seed_counts),
+            _dev(picks_d, torch.int64, "picks"), steps, OPERANDS[operands], blocks, cover_radius,
+            _dev(prio, torch.int32, "prio"),
+            _opt(picked if steps else None, torch.int64, "picked"),
+            _opt(gain if steps else None, torch.int32, "gain"),
+            _dev(theta, torch.float32, "theta"), _dev(covered, torch.int64, "covered"),
+            ctypes.c_void_p(stat.data_ptr()), _dev(ws, torch.uint8, "workspace"), need,
+            _stream(rows))
+        _check(rc, "dd_cover_greedy")
+        # the matrices written and read once, their bits written once
+        _t1(e0, "select", sum(8.0 * s * s + s * s / 8.0 for s in sizes), rows)
+    if check:
+        check_kcenter(stat.tolist())
+    return picked, gain, (theta, covered), stat
 
 
 def check_kcenter(stat):

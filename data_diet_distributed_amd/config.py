@@ -38,7 +38,10 @@ DEFAULTS = {
     "kcenter_seed_frac": 0.0,         # share of a quota seeded by the score (at least one seed)
     "kcenter_objective": "radius",    # radius (farthest-first) | inertia (greedy k-medoids)
     "kcenter_match": "none",          # none | mean (kernel herding: the kept mean tracks the group's)
-    "kcenter_ckpt": -1,               # the checkpoint whose feature rows the row-based
+    "kcenter_cover": "none",          # none | ball (greedy max coverage at a fixed radius)
+    "cover_radius": 0.25,             # the ball's squared radius, a share of the group's mean
+    #                                   squared pairwise distance (> 0; a convention, not tuned)
+    "kcenter_ckpt": -1,              # the checkpoint whose feature rows the row-based
     #                                   selections read (the kcenter fill, the d2 diversity)
     "select_diversity": "none",       # none | d2 (D2 pruning: message passing on the kNN graph)
     "d2_k": 10,                       # neighbours per example of the d2 graph (1..16)

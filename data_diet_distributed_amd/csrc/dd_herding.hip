@@ -8,13 +8,9 @@
 // Launches on one stream, no allocation, no synchronisation, nothing read back:
 //   pack, layout, matrix  dd_distmat.h: bit for bit the matrices dd_kmedoids_greedy builds.
 //   init    the groups' int64 sums = 0, picked = -1, value = -1.
-//   sums    workgroup (b, g) adds its slice of group g's rows in dd_class_feature_sums' 2^-24
-//           fixed point (thread k owns columns k, k + 256, ...; one 64-bit atomic per column and
-//           workgroup).  Integer sums are exact, so they do not depend on `blocks`.
-//   mean    mu[g][d] = (float)(((double)S[g][d] / n_g) * 2^-24), dd_class_centroids' formula.
-//   p       one row per wave: P_i = feat::wave_row_sqdist(f_i, mu_g) in fp32 (the fixed lane
-//           order and butterfly); a row with an element that is NaN, infinite or has |v| >= 2^15
-//           gets P = NaN (it never wins) and is counted in `bad`.
+//   sums, mean, p  dd_groupmean.h: the groups' exact fixed-point means mu and P_i = ||f_i - mu||^2
+//           in fp32; a row the fixed point cannot hold gets P = NaN (it never wins) and is
+//           counted in `bad`.
 //   select  ONE launch: workgroup g, 1024 threads, runs group g's whole loop.  Thread k owns rows
 //           k, k + 1024, ... of the group and keeps their A and P in REGISTERS (EPT = 1, 4 or 16
 //           rows per thread, by the largest group: 32 registers at 16 384 rows); LDS holds only
@@ -40,33 +36,17 @@
 // groups and where the group lies in the call change none of these values, so the picks are
 // bitwise independent of the launch geometry, the other groups, the chunk size, the lanes and the
 // world size.
-#include "dd_distmat.h"
+#include "dd_groupmean.h"
 
 namespace dd {
 namespace herding {
 
-using namespace distmat;
+using namespace groupmean;
 
 constexpr int kSelThreads = 1024;
 constexpr int kSelWaves = kSelThreads / kWave;
 constexpr int kMaxEpt = kMaxRows / kSelThreads;
-constexpr int kMaxBlocks = DD_KCENTER_MAX_BLOCKS;
-constexpr float kRange = 32768.f;      // |v| < 2^15: |q(v)| < 2^39 (dd_class_feature_sums' rule)
-constexpr double kScale = 16777216.0;  // 2^24
 static_assert(kMaxEpt == 16 && kMaxEpt * kSelThreads == kMaxRows, "16 rows per thread at most");
-
-// q(v) = round-to-nearest-even(v * 2^24); exact in double for |v| < 2^15
-__device__ __forceinline__ long long quantise(float v) {
-  return __double2ll_rn((double)v * kScale);
-}
-
-// workgroups per group of the sums launch (0: from the largest group and G alone)
-static int resolve_blocks(int64_t max_rows, int G, int blocks) {
-  if (blocks > 0) return blocks;
-  int64_t b = ceil_div(max_rows > 0 ? max_rows : 1, 64);  // at least 64 rows per workgroup
-  const int64_t cap = kTargetBlocks / G > 1 ? kTargetBlocks / G : 1;
-  return (int)(b > cap ? cap : b);
-}
 
 // the workspace: distmat::MatLayout, then the groups' sums, their means and P
 struct Layout : MatLayout {
@@ -91,64 +71,6 @@ __global__ __launch_bounds__(kThreads) void init_kernel(int64_t nsums, int64_t n
   if (i < nslots) {
     picked[i] = -1;
     value[i] = -1.f;
-  }
-}
-
-// Workgroup (b, g): rows [i0, i1) of group g, 256 columns at a time; an element outside the
-// range adds nothing (p_kernel counts its row, and the caller rejects the call's results).
-__global__ __launch_bounds__(kThreads) void sums_kernel(const float* __restrict__ rows,
-                                                        const int64_t* __restrict__ off, int D,
-                                                        long long* __restrict__ sums) {
-  const int g = blockIdx.y;
-  const int64_t r0 = off[g];
-  const int ng = (int)(off[g + 1] - r0);
-  const int chunk = (ng + (int)gridDim.x - 1) / (int)gridDim.x;
-  const int i0 = (int)blockIdx.x * chunk, i1 = i0 + chunk < ng ? i0 + chunk : ng;
-  if (i0 >= i1) return;  // (the whole workgroup)
-  for (int d = threadIdx.x; d < D; d += kThreads) {
-    const float* __restrict__ col = rows + r0 * (int64_t)D + d;
-    long long acc = 0;
-#pragma unroll 4
-    for (int i = i0; i < i1; ++i) {
-      const float v = col[i * (int64_t)D];
-      acc += fabsf(v) < kRange ? quantise(v) : 0ll;
-    }
-    if (acc != 0)
-      atomicAdd(reinterpret_cast<unsigned long long*>(sums + (int64_t)g * D + d),
-                (unsigned long long)acc);
-  }
-}
-
-__global__ __launch_bounds__(kThreads) void mean_kernel(const long long* __restrict__ sums,
-                                                        const int64_t* __restrict__ off,
-                                                        int64_t total, int D,
-                                                        float* __restrict__ mu) {
-  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= total) return;
-  const int64_t g = i / D;
-  const int64_t ng = off[g + 1] - off[g];
-  mu[i] = ng > 0 ? (float)(((double)sums[i] / (double)ng) * (1.0 / kScale)) : 0.f;
-}
-
-// one row per wave: workgroup (x, g) takes rows [4 x, 4 x + 4) of group g
-__global__ __launch_bounds__(kThreads) void p_kernel(const float* __restrict__ rows,
-                                                     const int64_t* __restrict__ off,
-                                                     const float* __restrict__ mu, int D,
-                                                     float* __restrict__ P,
-                                                     int* __restrict__ bad) {
-  const int g = blockIdx.y;
-  const int lane = threadIdx.x % kWave;
-  const int64_t r0 = off[g];
-  const int64_t i = (int64_t)blockIdx.x * kRows + threadIdx.x / kWave;
-  if (i >= off[g + 1] - r0) return;  // (a whole wave: the shuffles below stay within one wave)
-  const float* __restrict__ x = rows + (r0 + i) * (int64_t)D;
-  float oor = 0.f;
-  for (int d = lane; d < D; d += kWave) oor = fabsf(x[d]) < kRange ? oor : 1.f;
-  oor = group_max<kWave>(oor);
-  const float s = wave_row_sqdist(x, mu + (int64_t)g * D, D, lane, true, nullptr);
-  if (lane == 0) {
-    P[r0 + i] = oor != 0.f ? __builtin_nanf("") : s;
-    if (oor != 0.f) atomicAdd(bad, 1);
   }
 }
 
@@ -274,12 +196,7 @@ static void launch(const Args& a, char* ws, const Layout& L, hipStream_t st) {
   init_kernel<<<(unsigned)ceil_div(nsums > nslots ? nsums : nslots, kThreads), kThreads, 0, st>>>(
       nsums, nslots, sums, a.picked, a.value);
   if (L.max_rows == 0) return;  // every group is empty
-  sums_kernel<<<dim3((unsigned)a.blocks, (unsigned)a.G), kThreads, 0, st>>>(a.rows, a.off, a.D,
-                                                                            sums);
-  mean_kernel<<<(unsigned)ceil_div(nsums, kThreads), kThreads, 0, st>>>(sums, a.off, nsums, a.D,
-                                                                        mu);
-  p_kernel<<<dim3((unsigned)ceil_div(L.max_rows, kRows), (unsigned)a.G), kThreads, 0, st>>>(
-      a.rows, a.off, mu, a.D, P, a.bad);
+  launch_mean_p(a.rows, a.off, a.D, a.G, L.max_rows, a.blocks, sums, mu, P, a.bad, st);
   if (a.steps == 0) return;
   auto select = L.max_rows <= kSelThreads       ? &select_kernel<1>
                 : L.max_rows <= 4 * kSelThreads ? &select_kernel<4>

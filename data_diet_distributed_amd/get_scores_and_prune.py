@@ -440,7 +440,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                   fast: bool = True, refine="auto", policy="global", skip=0, score="el2n",
                   knn_k=5, fill="score", seed_frac=0.0, kmeans_k=0, kmeans_iters=20,
                   objective="radius", maha_shrink=0.01, diversity="none", d2_k=10,
-                  d2_gamma_f=1.0, d2_gamma_r=1.0, kde_bandwidth=0.25, match="none"):
+                  d2_gamma_f=1.0, d2_gamma_r=1.0, kde_bandwidth=0.25, match="none",
+                  cover="none", cover_radius=0.25):
     """Reference-compatible: returns (DataLoader over the kept Subset, samples).
 
     fast=False forces the general `net(input)` path (same batches, same selection).
@@ -489,6 +490,12 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     kernel herding instead, every pick the example that brings the mean of its group's kept rows
     closest to the group's mean (dd_herding_greedy; fill="kcenter", objective="radius" and the
     same group limit); the record holds each group's mean_gap and no radius.
+    cover / cover_radius (ScoreConfig.kcenter_cover / cover_radius; both checked whatever the
+    fill): "ball" keeps the kcenter fill's seeds and quotas and picks by greedy maximum coverage
+    at a fixed radius instead, every pick the example whose ball holds the most examples not yet
+    within theta = cover_radius x (the group's mean squared pairwise distance) of a kept one, a
+    tie to the better score (dd_cover_greedy; fill="kcenter", objective="radius", match="none"
+    and the same group limit); the record holds each group's theta and coverage and no radius.
     diversity / d2_k / d2_gamma_f / d2_gamma_r (ScoreConfig.select_diversity and its fields; the
     three numbers are checked whatever the diversity): "d2" is D2 pruning on the d2_k-nearest-
     neighbour graph of the visited examples' feature rows: a score absorbs its neighbours' (edge
@@ -498,8 +505,8 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     "variability", "grand" and "proto" need K checkpoints / a backward pass / the class means
     over the whole set: the engine (scoring.ScoringEngine) computes them.  refine=True needs
     score="el2n"."""
-    from .methods import (check_bandwidth, check_diversity, check_match, check_objective,
-                          check_selection, check_shrink)
+    from .methods import (check_bandwidth, check_cover, check_diversity, check_match,
+                          check_objective, check_selection, check_shrink)
     from .scoring import normalize_refine, select_with_policy
     refine = normalize_refine(refine)
     if score in ("variability", "grand", "proto"):
@@ -528,6 +535,9 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
     check_objective(objective, "objective")
     check_match(match, fill, objective, name="match", fill_name="fill",
                 objective_name="objective")
+    cover, cover_radius = check_cover(cover, cover_radius, fill, objective, match, name="cover",
+                                      fill_name="fill", objective_name="objective",
+                                      match_name="match")
     d2_k, d2_gamma_f, d2_gamma_r = check_diversity(
         diversity, d2_k, d2_gamma_f, d2_gamma_r, fill, skip, name="diversity", fill_name="fill",
         skip_name="skip")
@@ -575,7 +585,7 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
         pos, sparse_loader.last_selection = select_with_policy(
             scores.contiguous(), labels_visit, ncls, samples, policy, int(skip), fill=fill,
             seed_frac=seed_frac, rows=seen["rows"] if kcenter else None, objective=objective,
-            match=match,
+            match=match, cover=cover, cover_radius=cover_radius,
             diversity=diversity, d2_k=d2_k, gamma_f=d2_gamma_f, gamma_r=d2_gamma_r)
         kept = visit[pos]
     elif fp is not None and refine is True and 0 < samples < scores.numel():
@@ -620,9 +630,13 @@ def sparse_loader(train_loader, train_samples, net, device, sparsity, batch_size
                                 "class_seeds": sparse_loader.last_selection["class_seeds"],
                                 **({"radius": json_radius(
                                     sparse_loader.last_selection["radius"])}
-                                   if match == "none" else {
+                                   if match == "none" and cover == "none" else {
                                        "kcenter_match": match,
-                                       "mean_gap": sparse_loader.last_selection["mean_gap"]})}),
+                                       "mean_gap": sparse_loader.last_selection["mean_gap"]}
+                                   if cover == "none" else {
+                                       "kcenter_cover": cover, "cover_radius": cover_radius,
+                                       "theta": sparse_loader.last_selection["theta"],
+                                       "coverage": sparse_loader.last_selection["coverage"]})}),
                             **({} if fill != "kcenter" or objective == "radius" else {
                                 "kcenter_objective": objective,
                                 "inertia": json_radius(

@@ -185,6 +185,37 @@ def check_match(match, fill="kcenter", objective="radius", *, name="kcenter_matc
     return match
 
 
+# Whether the centre-based fill ("kcenter") covers at a FIXED radius instead of minimising one:
+#   "none"  the fill picks by kcenter_objective / kcenter_match
+#   "ball"  greedy maximum coverage (ProbCover, Yehuda et al.): with theta = cover_radius times
+#           the group's mean squared pairwise distance, every pick is the row whose theta-ball
+#           holds the most rows not yet within theta of a kept row, a tie to the better score
+#           (dd_cover_greedy).  The seeds, the groups and the quotas are the fill's.
+KCENTER_COVER = ("none", "ball")
+
+
+def check_cover(cover, radius, fill="kcenter", objective="radius", match="none", *,
+                name="kcenter_cover", radius_name="cover_radius", fill_name="select_fill",
+                objective_name="kcenter_objective", match_name="kcenter_match"):
+    """ScoreConfig's kcenter_cover and cover_radius, and select_with_policy's / sparse_loader's
+    `cover` and `cover_radius` under their own names: one of KCENTER_COVER and a finite number
+    > 0 (both checked whatever the fill); "ball" replaces the picks of the kcenter fill, so it
+    needs that fill, the default objective and no match.  Returns (cover, radius as a float)."""
+    if cover not in KCENTER_COVER:
+        raise ValueError(f"{name} must be one of {KCENTER_COVER} (got {cover!r})")
+    radius = check_bandwidth(radius, radius_name)
+    if cover == "ball" and fill != "kcenter":
+        raise ValueError(f"{name}='ball' needs {fill_name}='kcenter' (got {fill!r}): the cover "
+                         f"fills the quotas of the centre-based fill")
+    if cover == "ball" and objective != "radius":
+        raise ValueError(f"{name}='ball' needs {objective_name}='radius', the default (got "
+                         f"{objective!r}): the picks follow one rule")
+    if cover == "ball" and match != "none":
+        raise ValueError(f"{name}='ball' needs {match_name}='none', the default (got "
+                         f"{match!r}): the picks follow one rule")
+    return cover, radius
+
+
 # Whether the rank cut (select_fill "score") also weighs coverage:
 #   "none"  the rank cut as it is
 #   "d2"    D2 pruning (Maharana, Yadav & Bansal): the examples sit on the d2_k-nearest-neighbour

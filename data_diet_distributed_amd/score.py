@@ -26,7 +26,9 @@ rest (config.DEFAULTS):
                      of a quota seeded by the score; kcenter_ckpt: whose rows (default: the last);
                      kcenter_objective: radius (farthest-first) | inertia (greedy k-medoids,
                      --fill-objective); kcenter_match: none | mean (kernel herding: the kept rows'
-                     mean tracks the group's, --fill-match)
+                     mean tracks the group's, --fill-match); kcenter_cover: none | ball (greedy
+                     maximum coverage at the fixed radius cover_radius, --fill-cover,
+                     --cover-radius)
   select_diversity   none | d2: D2 pruning on the d2_k-nearest-neighbour graph of kcenter_ckpt's
                      feature rows (--diversity, --d2-k); d2_gamma_f / d2_gamma_r: the forward /
                      reverse edge weights' sharpness (--d2-gamma-f, --d2-gamma-r)
@@ -158,6 +160,8 @@ def engine_config(cfg):
                        kcenter_ckpt=int(cfg.get("kcenter_ckpt", -1)),
                        kcenter_objective=cfg.get("kcenter_objective", "radius"),
                        kcenter_match=cfg.get("kcenter_match", "none"),
+                       kcenter_cover=cfg.get("kcenter_cover", "none"),
+                       cover_radius=cfg.get("cover_radius", 0.25),
                        select_diversity=cfg.get("select_diversity", "none"),
                        d2_k=cfg.get("d2_k", 10), d2_gamma_f=cfg.get("d2_gamma_f", 1.0),
                        d2_gamma_r=cfg.get("d2_gamma_r", 1.0),
@@ -227,6 +231,9 @@ def score_from_config(cfg: dict, sparsity: float, out_path=None, log=print):
                         radius=None if sel["radius"] is None else json_radius(sel["radius"]))
             if sel.get("match", "none") != "none":  # (the default: metadata unchanged)
                 meta.update(kcenter_match=sel["match"], mean_gap=sel["mean_gap"])
+            if sel.get("cover", "none") != "none":  # (the default: metadata unchanged)
+                meta.update(kcenter_cover=sel["cover"], cover_radius=sel["cover_radius"],
+                            theta=sel["theta"], coverage=sel["coverage"])
             if sel.get("objective", "radius") != "radius":  # (the default: metadata unchanged)
                 meta.update(kcenter_objective=sel["objective"],
                             inertia=json_radius(sel["inertia"]))
@@ -267,6 +274,12 @@ def parse(argv=None):
     ap.add_argument("--fill-match", default=None, choices=("none", "mean"),
                     help="whether the kcenter fill matches its group's mean instead (kernel "
                          "herding; default: kcenter_match of the config)")
+    ap.add_argument("--fill-cover", default=None, choices=("none", "ball"),
+                    help="whether the kcenter fill covers at a fixed radius instead (greedy "
+                         "maximum coverage; default: kcenter_cover of the config)")
+    ap.add_argument("--cover-radius", type=float, default=None,
+                    help="the ball's squared radius as a share of the group's mean squared "
+                         "pairwise distance (default: cover_radius of the config)")
     ap.add_argument("--diversity", default=None, choices=("none", "d2"),
                     help="whether the score fill weighs coverage (default: select_diversity of "
                          "the config)")
@@ -287,7 +300,8 @@ def apply_overrides(cfg: dict, args) -> dict:
     place)."""
     for key, v in (("select_policy", args.policy), ("select_skip", args.skip),
                    ("select_fill", args.fill), ("kcenter_objective", args.fill_objective),
-                   ("kcenter_match", args.fill_match),
+                   ("kcenter_match", args.fill_match), ("kcenter_cover", args.fill_cover),
+                   ("cover_radius", args.cover_radius),
                    ("select_diversity", args.diversity), ("d2_k", args.d2_k),
                    ("d2_gamma_f", args.d2_gamma_f), ("d2_gamma_r", args.d2_gamma_r),
                    ("kde_bandwidth", args.kde_bandwidth)):

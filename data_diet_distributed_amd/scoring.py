@@ -53,7 +53,7 @@ from .methods import (CLUSTER_METHODS, COVARIANCE_METHODS, DENSITY_METHODS,  # n
                       FORWARD_FAMILY, FORWARD_SCORES, KNN_METHODS, LOGIT_FAMILY, LOGIT_METHODS, NEIGHBOR_METHODS,
                       SELECT_DIVERSITY, SELECT_FILLS, SELECT_POLICIES, check_bandwidth,
                       check_diversity, check_fill,
-                      check_match, check_objective, check_selection, check_shrink, known, pass_of, refinable,
+                      check_cover, check_match, check_objective, check_selection, check_shrink, known, pass_of, refinable,
                       seed_counts)
 from .resnet import ResNet
 
@@ -176,11 +176,22 @@ class ScoreConfig:
     # persistent workgroup; groups of at most _capi.KMEDOIDS_MAX_GROUP_ROWS rows).  It needs
     # select_fill = "kcenter" and the default objective; last_selection records each group's
     # mean_gap = || mean(group) - mean(kept) ||_2 and no radius.
+    # kcenter_cover (methods.KCENTER_COVER): "ball" keeps the fill's groups, quotas and seeds and
+    # picks by greedy maximum coverage at a FIXED radius instead (ProbCover; dd_cover_greedy, the
+    # distances thresholded into bits once and a group's whole loop in one persistent workgroup;
+    # groups of at most _capi.KMEDOIDS_MAX_GROUP_ROWS rows): each pick is the row whose ball holds
+    # the most rows not yet within the radius of a kept row, a tie to the better select_by score.
+    # The ball's squared radius is cover_radius times the group's mean squared pairwise distance;
+    # the default 0.25 is a convention like kde_bandwidth's, tuned against nothing.  It needs
+    # select_fill = "kcenter", the default objective and no match; last_selection records each
+    # group's theta and coverage and no radius.  Both are validated whatever the fill.
     select_fill: str = "score"
     kcenter_seed_frac: float = 0.0
     kcenter_ckpt: int = -1
     kcenter_objective: str = "radius"
     kcenter_match: str = "none"
+    kcenter_cover: str = "none"
+    cover_radius: float = 0.25
     # Whether the score fill also weighs coverage (methods.SELECT_DIVERSITY): "d2" is D2 pruning:
     # on the d2_k-nearest-neighbour graph of checkpoint kcenter_ckpt's feature rows a score first
     # absorbs its neighbours' (edge weights exp(-d2_gamma_f d^2 / mean d^2)), then the quotas of
@@ -240,6 +251,9 @@ class ScoreConfig:
         self.kcenter_seed_frac = float(self.kcenter_seed_frac)
         check_objective(self.kcenter_objective)
         check_match(self.kcenter_match, self.select_fill, self.kcenter_objective)
+        _, self.cover_radius = check_cover(self.kcenter_cover, self.cover_radius,
+                                           self.select_fill, self.kcenter_objective,
+                                           self.kcenter_match)
         if isinstance(self.kcenter_ckpt, bool) or not isinstance(self.kcenter_ckpt,
                                                                  (int, np.integer)):
             raise ValueError(f"kcenter_ckpt must be an integer (got {self.kcenter_ckpt!r})")
@@ -317,7 +331,8 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
                        skip: int = 0, check_nan: bool = True, fill: str = "score",
                        seed_frac: float = 0.0, rows: Optional[torch.Tensor] = None,
                        objective: str = "radius", diversity: str = "none", d2_k: int = 10,
-                       gamma_f: float = 1.0, gamma_r: float = 1.0, match: str = "none"):
+                       gamma_f: float = 1.0, gamma_r: float = 1.0, match: str = "none",
+                       cover: str = "none", cover_radius: float = 0.25):
     """The keep-set of `k` of the n = keys.numel() examples under a selection policy
     (ScoreConfig.select_policy / select_skip), in dd_select_topk's order: key descending, ties
     by ascending index.  `labels` (int64 [n], on the keys' device) and `num_classes` are read
@@ -355,6 +370,17 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     from the rows (None for a group that keeps nothing), and its "radius" stays None.  The group
     limit and its error under "global" are objective="inertia"'s.
 
+    cover="ball" (ScoreConfig.kcenter_cover / cover_radius; needs fill = "kcenter", objective =
+    "radius" and match = "none"; both are checked always): dd_cover_greedy makes the picks instead,
+    each the row whose ball holds the most rows not yet within theta of a kept row, theta =
+    cover_radius times the group's mean squared pairwise distance; a tie goes to the row that
+    ranks higher in its group by (key descending, index ascending), computed on the device, so
+    once everything is covered the quota is filled in score order.  The seeds and the order of
+    `kept` are as above; the record gets "cover", "cover_radius", "theta" (per group) and
+    "coverage", per group the share of its rows within theta of a kept row (None for an empty
+    group), from the same one read, and its "radius" stays None.  The group limit and its error
+    under "global" are objective="inertia"'s.
+
     diversity="d2" (ScoreConfig.select_diversity; needs fill = "score", skip = 0 and `rows`): D2
     pruning.  The groups and quotas are the policy's ("global": one group with quota k).  dd_knn
     gives every row its d2_k nearest other rows of `rows` (nbr_id, dist); scale = the float64 mean
@@ -375,6 +401,9 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     check_objective(objective, "objective")
     check_match(match, fill, objective, name="match", fill_name="fill",
                 objective_name="objective")
+    cover, cover_radius = check_cover(cover, cover_radius, fill, objective, match, name="cover",
+                                      fill_name="fill", objective_name="objective",
+                                      match_name="match")
     d2_k, gamma_f, gamma_r = check_diversity(
         diversity, d2_k, gamma_f, gamma_r, fill, skip, name="diversity", k_name="d2_k",
         gamma_f_name="gamma_f", gamma_r_name="gamma_r", fill_name="fill", skip_name="skip")
@@ -395,19 +424,23 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
             rec.update(objective=objective, inertia=None)
         if match != "none":
             rec.update(match=match, mean_gap=None)
+        if cover != "none":
+            rec.update(cover=cover, cover_radius=cover_radius, theta=None, coverage=None)
         if rows is None or rows.dim() != 2 or rows.shape[0] != n:
             raise ValueError(f"fill='kcenter' needs rows [n = {n}, D] (got "
                              f"{None if rows is None else tuple(rows.shape)})")
     if policy == "global":
         if fill == "kcenter":
-            if (objective == "inertia" or match == "mean") and n > _capi.KMEDOIDS_MAX_GROUP_ROWS:
-                what = "objective='inertia'" if objective == "inertia" else "match='mean'"
+            if ((objective == "inertia" or match == "mean" or cover == "ball")
+                    and n > _capi.KMEDOIDS_MAX_GROUP_ROWS):
+                what = ("objective='inertia'" if objective == "inertia"
+                        else "match='mean'" if match == "mean" else "cover='ball'")
                 raise ValueError(f"{what} under policy='global' holds one n x n "
                                  f"distance matrix: n = {n} is above "
                                  f"{_capi.KMEDOIDS_MAX_GROUP_ROWS}; use a class policy "
                                  f"('stratified' or 'balanced'), whose groups are the classes")
             return _kcenter_fill(keys, None, [n], [k], rows.contiguous(), seed_frac, rec,
-                                 check_nan, objective, match)
+                                 check_nan, objective, match, cover, cover_radius)
         if d2:
             return _d2_fill(keys, None, [k], rows.contiguous(), d2_k, gamma_f, gamma_r, rec,
                             check_nan)
@@ -425,7 +458,7 @@ def select_with_policy(keys: torch.Tensor, labels, num_classes, k: int, policy: 
     rec.update(class_counts=n_c, class_skip=s, class_quota=q)
     if fill == "kcenter":
         return _kcenter_fill(keys, labels, n_c, q, rows.contiguous(), seed_frac, rec, check_nan,
-                             objective, match)
+                             objective, match, cover, cover_radius)
     if d2:
         if C > _capi.D2_MAX_GROUPS:
             raise ValueError(f"diversity='d2' holds at most {_capi.D2_MAX_GROUPS} groups "
@@ -472,10 +505,10 @@ def _d2_fill(keys, labels, quotas, rows, d2_k, gamma_f, gamma_r, rec, check_nan)
 
 
 def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan,
-                  objective="radius", match="none"):
+                  objective="radius", match="none", cover="none", cover_radius=0.25):
     """select_with_policy's kcenter fill over the groups `labels` (None: one group) of `sizes`
-    members with `quotas`, the picks by `objective` (by herding with match="mean"); completes and
-    returns (kept, rec)."""
+    members with `quotas`, the picks by `objective` (by herding with match="mean", by maximum
+    coverage with cover="ball"); completes and returns (kept, rec)."""
     G, dev = len(sizes), keys.device
     m = seed_counts(quotas, seed_frac)
     if labels is None:
@@ -484,7 +517,10 @@ def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan,
         seeds, nan, _ = _capi.select_topk_by_class(keys, labels, G, [0] * G, m, k_total=sum(m),
                                                    check=False)
     picks = [q - a for q, a in zip(quotas, m)]
-    if match == "mean":
+    if cover == "ball":
+        def greedy(*args, **kw):
+            return _capi.cover_greedy(*args, _score_rank(keys, labels, sizes), cover_radius, **kw)
+    elif match == "mean":
         greedy = _capi.herding_greedy
     else:
         greedy = _capi.kmedoids_greedy if objective == "inertia" else _capi.kcenter_greedy
@@ -497,6 +533,16 @@ def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan,
     if match == "mean":
         return kept, _mean_gap_record(rows, labels, sizes, quotas, kept, m, nan, stat, rec,
                                       check_nan)
+    if cover == "ball":
+        theta, covered = mind2
+        host = torch.cat([nan.to(torch.float64), stat.to(torch.float64), theta.to(torch.float64),
+                          covered.to(torch.float64)]).tolist()  # the one read after the loop
+        if check_nan and host[0]:
+            raise ValueError(f"{int(host[0])} NaN score(s): the keep-set is undefined")
+        _capi.check_kcenter(host[1:3])
+        rec.update(class_seeds=m, theta=host[3:3 + G],
+                   coverage=[c / s if s else None for c, s in zip(host[3 + G:], sizes)])
+        return kept, rec
     # the covering radius per group: the largest squared distance left (kept rows hold -1)
     far = torch.zeros(G, dtype=torch.float32, device=dev)
     grp = labels if labels is not None else torch.zeros(keys.numel(), dtype=torch.int64,
@@ -517,6 +563,23 @@ def _kcenter_fill(keys, labels, sizes, quotas, rows, seed_frac, rec, check_nan,
     if objective == "inertia":
         rec.update(inertia=[float(v) for v in host[3 + G:]])
     return kept, rec
+
+
+def _score_rank(keys, labels, sizes):
+    """int32 [n] on the device: every example's rank in its group (`labels`; None: one group) by
+    (key descending, index ascending), the cover fill's tie-break.  Two stable sorts, no read."""
+    n, dev = keys.numel(), keys.device
+    order = torch.argsort(keys, descending=True, stable=True)
+    rank = torch.arange(n, dtype=torch.int64, device=dev)
+    if labels is not None:
+        grp = labels[order]
+        by_group = torch.argsort(grp, stable=True)
+        order, grp = order[by_group], grp[by_group]
+        starts = np.cumsum([0] + list(sizes[:-1]), dtype=np.int64)
+        rank = rank - torch.from_numpy(starts).to(dev)[grp]
+    prio = torch.empty(n, dtype=torch.int32, device=dev)
+    prio[order] = rank.to(torch.int32)
+    return prio
 
 
 def _mean_gap_record(rows, labels, sizes, quotas, kept, m, nan, stat, rec, check_nan):
@@ -1198,6 +1261,7 @@ class ScoringEngine:
                 keys, all_labels, self.models[0].linear.out_features, k, c.select_policy,
                 c.select_skip, check_nan, fill=c.select_fill, seed_frac=c.kcenter_seed_frac,
                 objective=c.kcenter_objective, match=c.kcenter_match,
+                cover=c.kcenter_cover, cover_radius=c.cover_radius,
                 diversity=c.select_diversity, d2_k=c.d2_k,
                 gamma_f=c.d2_gamma_f, gamma_r=c.d2_gamma_r,
                 rows=self._kcenter_rows if c.row_selection() is not None else None)

@@ -1064,6 +1064,65 @@ int dd_herding_greedy(const float* rows, const int64_t* ids, int64_t n, int32_t 
                       void* stream);
 
 /* ---------------------------------------------------------------------------------------- *
+ * Ball cover (the max-coverage rule of ProbCover: Yehuda et al., "Active learning through a
+ * covering lens") over feature rows, inside groups: the dual of dd_kcenter_greedy.  The radius is
+ * fixed and every pick maximises the number of rows within it of a kept row.  Purely additive:
+ * dd_abi_version() stays 10.
+ *
+ * rows, ids, off, sizes, seeds, seed_off, max_seeds, picks, steps, operands and blocks are
+ * dd_herding_greedy's, M is dd_kmedoids_greedy's matrix and mu, P_i are dd_herding_greedy's, all
+ * bit for bit (shared builders).  A row is VALID when no element is NaN, infinite or has
+ * |v| >= 2^15.  Inside one group of n_g rows:
+ *
+ *   theta     = (float)(cover_radius * (2 / n_g) * sum_i P_i) in float64 over the valid rows, the
+ *               sum in an order n_g alone fixes: cover_radius times the group's mean squared
+ *               pairwise distance.  theta[g] returns it (0 for an empty group).
+ *   adj[i][j] = (M[i][j] <= theta) for valid i and j, adj[i][i] = 1 for a valid i, 0 otherwise.
+ *   uncovered = the valid rows;  deg_i = popcount(adj_i & uncovered).
+ *   cover(j):   new = adj_j & uncovered;  uncovered &= ~adj_j;  deg_i -= popcount(adj_i & new) for
+ *               every i;  row j is kept from here on.
+ *   The seeds are covered in ascending position (a seed outside its group is ignored), then
+ *   step t of group g (t < picks[g]): of the unkept valid rows the one with the largest deg_i is
+ *               taken, a tie to the smaller prio_i.  prio is an int32 per row (in the order of
+ *               `rows`), unique within its group and in [0, 2^14).
+ *               picked[t][g] = its id,  gain[t][g] = its deg,  then cover(it).
+ *   and (t, g) with t >= picks[g]: picked = -1, gain = -1.  Once every row is covered the picks go
+ *   by prio alone, with gain 0.  covered[g] = the valid rows that are not in `uncovered` at the
+ *   end.  After the one compare with theta everything is integer arithmetic.
+ *   bad[0] += the rows of the groups that are not valid.  Such a row is never picked and covers
+ *   nothing; the caller clears bad and rejects the call's results when it is non-zero.
+ *
+ * Launches (all on `stream`, nothing read back, no allocation): the pack and the matrices as in
+ * dd_kmedoids_greedy; one init; the sums, the means and P as in dd_herding_greedy; theta (one
+ * workgroup per group); the bits (a wave per 64 floats of a row of M: load, compare, ballot, one
+ * 64-bit store; M is not read again); then ONE select launch of G workgroups of 1024 threads.
+ * Workgroup g runs group g's whole loop: a thread keeps deg and the tie-break key of its rows (up
+ * to 16) in registers, `uncovered` and `new` are 256 64-bit words each in LDS, a pick is a maximum
+ * through a wave butterfly and sixteen LDS entries with one workgroup barrier, and the update
+ * reads only the words in which `new` is non-zero.  No launch per pick, and no kernel waits for
+ * another workgroup.
+ *
+ * Invariance: every output is bitwise independent of blocks, the rows' placement, the other groups
+ * and their layout.
+ *
+ * Limits: dd_herding_greedy's (0 <= sizes[g] <= DD_KMEDOIDS_MAX_GROUP_ROWS), and cover_radius
+ * finite and > 0.  Outside them, a NULL buffer the call would touch or a workspace below
+ * dd_cover_workspace_bytes or not 16-byte aligned is DD_EINVAL with a message before any launch.
+ * n == 0 returns DD_OK.  The workspace (host only; 0 for bad arguments) holds dd_herding_greedy's,
+ * then 4 G bytes of theta and one bit per float of the matrices, each region rounded up to 256.
+ * ---------------------------------------------------------------------------------------- */
+size_t dd_cover_workspace_bytes(int64_t n, int32_t D, int32_t G, const int64_t* sizes,
+                                int64_t steps, int32_t operands);
+
+int dd_cover_greedy(const float* rows, const int64_t* ids, int64_t n, int32_t D,
+                    const int64_t* off, const int64_t* sizes, int32_t G, const int64_t* seeds,
+                    const int64_t* seed_off, int64_t max_seeds, const int64_t* picks,
+                    int64_t steps, int32_t operands, int32_t blocks, double cover_radius,
+                    const int32_t* prio, int64_t* picked, int32_t* gain, float* theta,
+                    int64_t* covered, int32_t* bad, void* workspace, size_t workspace_bytes,
+                    void* stream);
+
+/* ---------------------------------------------------------------------------------------- *
  * D2 pruning (Maharana, Yadav & Bansal, "D2 Pruning: Message Passing for Balancing Diversity and
  * Difficulty in Data Pruning") on a k-nearest-neighbour graph: the keep-set that weighs difficulty
  * against coverage.  Purely additive: dd_abi_version() stays 10.
